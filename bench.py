@@ -1,6 +1,6 @@
 """Flagship benchmark: Librispeech Conformer-L train step (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Measures whole-job examples/sec for the Conformer-L ASR train step on
 synthetic Librispeech-shaped data (random-init weights, bf16 compute),
@@ -12,6 +12,18 @@ in a child process per mode (hipGraph first, eager fallback) so a GPU
 memory fault in the captured path degrades to a slower eager number
 instead of an rc=134 abort with no JSON. Phase markers go to stderr so a
 crash is attributable to model-build / warmup / capture / replay-N.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps steps, optionally write --dump-outputs, print the one JSON
+result line. Anything beyond that belongs behind --full (nothing does
+today: peak memory, the profiler table and the decode measurement are
+already opt-in through --memory, --profile and --decode).
+
+--dump-outputs DIR writes what the last timed step computed as float32
+DIR/<name>.npy: every metric the step returns (value and weight) and a
+fixed, seeded sample of the updated parameters. Inputs, init and dropout
+seeds are fixed, so two builds run with the same arguments can be
+compared output for output.
 """
 
 from __future__ import annotations
@@ -71,6 +83,16 @@ def build_argparser():
                        'decode_num_hyps; greedy when 1).')
   ap.add_argument('--decode-hyps', type=int, default=1,
                   help='Beam width for --decode.')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='After the timed steps, write the outputs of the '
+                       'last timed step (metrics, and a seeded sample of '
+                       'the updated parameters) as float32 DIR/<name>.npy.')
+  ap.add_argument('--full', action='store_true',
+                  help='Also run the measurements and checks that the '
+                       'headline figure does not need. A plain run only '
+                       'sets up, warms up, times --steps steps and prints '
+                       'the result line; no extra measurement exists '
+                       'today, so this currently adds nothing.')
   return ap
 
 
@@ -99,6 +121,10 @@ def main():
       base.append('--memory')
     if args.profile:
       base += ['--profile', args.profile]
+    if args.dump_outputs:
+      base += ['--dump-outputs', os.path.abspath(args.dump_outputs)]
+    if args.full:
+      base.append('--full')
     for mode in ('graph', 'eager'):
       _phase(f'launching child mode={mode}')
       proc = subprocess.run(base + ['--mode', mode],
@@ -122,6 +148,61 @@ def main():
     sys.exit(1)
 
   run_bench(args, world)
+
+
+# --dump-outputs budget: any one array above 4M elements (16 MB as
+# float32) is stored as a fixed, seeded sample of that size, and the whole
+# dump must stay below 64 MB.
+_DUMP_SAMPLE_ELEMS = 4 * 1024 * 1024
+_DUMP_MAX_BYTES = 64 * 1024 * 1024
+
+
+def _seeded_sample(flat):
+  """`flat` itself when small, else a fixed seeded sample of its elements
+  (the same indices for every run with the same element count)."""
+  import torch
+  if flat.numel() <= _DUMP_SAMPLE_ELEMS:
+    return flat
+  g = torch.Generator().manual_seed(20240)
+  idx = torch.randint(0, flat.numel(), (_DUMP_SAMPLE_ELEMS,), generator=g)
+  return flat[idx.to(flat.device)]
+
+
+def _dump_arrays(dump_dir, named):
+  """Writes (name, tensor-or-number) pairs as float32 DIR/<name>.npy."""
+  import numpy as np
+  import torch
+  os.makedirs(dump_dir, exist_ok=True)
+  total = 0
+  for name, val in named:
+    if isinstance(val, torch.Tensor):
+      val = val.detach()
+      if val.numel() > _DUMP_SAMPLE_ELEMS:
+        val = _seeded_sample(val.reshape(-1))
+      arr = val.to(torch.float32).cpu().numpy()
+    elif isinstance(val, (bool, int, float)):
+      arr = np.asarray(val, dtype=np.float32)
+    else:
+      continue
+    total += arr.nbytes
+    if total > _DUMP_MAX_BYTES:
+      raise RuntimeError(f'--dump-outputs: over {_DUMP_MAX_BYTES} bytes '
+                         f'at {name}')
+    fname = name.replace('[', '.').replace(']', '').replace('/', '_')
+    np.save(os.path.join(dump_dir, fname + '.npy'), arr)
+  _phase(f'dumped {total} bytes of outputs to {dump_dir}')
+
+
+def _step_outputs(task, metrics):
+  """What a caller of the train step is left with: the returned metrics
+  ((value, weight) per name) and the parameters the step updated, the
+  latter flattened in name order and sampled to a fixed size."""
+  import torch
+  from lingvo_amd.core.nested_map import NestedMap
+  named = sorted(task.named_parameters(), key=lambda kv: kv[0])
+  flat = torch.cat([prm.detach().reshape(-1).float() for _, prm in named])
+  return (NestedMap(metrics).FlattenItems() +
+          [('params_sample', _seeded_sample(flat))])
 
 
 def run_decode_bench(args):
@@ -163,6 +244,9 @@ def run_decode_bench(args):
   if has_gpu:
     torch.cuda.synchronize()
   elapsed = time.perf_counter() - t0
+  if args.dump_outputs:
+    from lingvo_amd.core.nested_map import NestedMap
+    _dump_arrays(args.dump_outputs, NestedMap(out).FlattenItems())
   examples_per_sec = args.batch * args.steps / elapsed
   print(json.dumps({
       'metric': 'decode examples/sec, Librispeech Conformer-L',
@@ -282,6 +366,11 @@ def run_bench(args, world):
     e = torch.tensor([elapsed], device=device if has_gpu else 'cpu')
     dist.all_reduce(e, op=dist.ReduceOp.MAX)
     elapsed = float(e.item())
+
+  # Before anything below steps again: `metrics` still holds what the
+  # last timed step returned (graph replays overwrite it in place).
+  if args.dump_outputs and rank == 0:
+    _dump_arrays(args.dump_outputs, _step_outputs(task, metrics))
 
   peak_mem_gb = None
   if args.memory and has_gpu:

@@ -77,6 +77,52 @@ def test_bench_harness_cpu():
   assert rec['value'] > 0
 
 
+def test_bench_dump_outputs_cpu(tmp_path):
+  """--dump-outputs writes the last timed step's outputs as float .npy,
+  identically from run to run; --full is accepted; --steps sets the
+  number of timed steps."""
+  import numpy as np
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  dumps = []
+  for name, extra in (('a', []), ('b', ['--full'])):
+    out_dir = tmp_path / name
+    res = subprocess.run(
+        [sys.executable, 'bench.py', '--gpus', '1', '--steps', '2',
+         '--warmup', '1', '--batch', '2', '--dump-outputs', str(out_dir)]
+        + extra,
+        cwd=root, env=dict(os.environ), capture_output=True, text=True,
+        timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    rec = json.loads(res.stdout.strip().splitlines()[-1])
+    assert rec['steps'] == 2 and rec['ms_per_step'] > 0
+    files = sorted(f for f in os.listdir(out_dir) if f.endswith('.npy'))
+    assert 'loss.0.npy' in files and 'params_sample.npy' in files
+    arrays = {f: np.load(out_dir / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64)
+               for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+    assert np.isfinite(arrays['loss.0.npy']).all()
+    assert abs(float(arrays['loss.0.npy']) -
+               rec['config']['final_loss']) < 1e-3
+    dumps.append((rec['dtype'], arrays))
+  (dtype, a), (_, b) = dumps
+  assert a.keys() == b.keys()
+  for f in a:
+    assert a[f].shape == b[f].shape, f
+    if dtype == 'fp32':
+      # CPU fp32 steps on identical inputs are bit-reproducible.
+      np.testing.assert_array_equal(a[f], b[f], err_msg=f)
+    elif f != 'params_sample.npy':
+      # On a GPU the bf16 step accumulates with atomics, so two runs on
+      # identical inputs differ in summation order only: far below one
+      # bf16 epsilon (2^-8) on a scalar metric. Different inputs or
+      # seeds would move the loss by much more than that.
+      np.testing.assert_allclose(a[f], b[f], rtol=2.0**-8, atol=2.0**-8,
+                                 err_msg=f)
+    else:
+      assert np.isfinite(a[f]).all() and np.isfinite(b[f]).all()
+
+
 def test_conformer_layer_streaming_matches_fprop():
   """Causal ConformerLayer chunked StreamStep == full FProp."""
   import torch
