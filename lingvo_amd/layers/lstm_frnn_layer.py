@@ -9,6 +9,12 @@ state carry run in the fused K11 kernel, so each scan step is one
 small GEMM + one fused kernel instead of ~10 elementwise launches —
 this is what makes the LAS biLSTM stack viable without hipGraph
 capture (HIP rejects the full-scan graph; see docs/KERNEL_NOTES.md).
+
+With `fused_scan` set (and an eligible configuration, see
+_FusedScanEligible) the whole recurrence instead runs through
+ops.lstm_scan: one HIP launch per timestep for all directions, forward
+and backward, with the recurrent GEMM, the gate math and the padded
+carry in the same kernel.
 """
 
 from __future__ import annotations
@@ -77,6 +83,53 @@ class LSTMCellSimpleExt(rnn_cell.LSTMCellSimple):
     return NestedMap(c=c1, m=m1)
 
 
+def _FusedScanEligible(cells, inputs: torch.Tensor) -> bool:
+  """True when ops.lstm_scan computes exactly what the Recurrent loop
+  over `cells` would: plain LSTMCellSimpleExt (no CIFG, no projection,
+  tanh output, no ZoneOut), H % 32 == 0 for the MFMA tiles, identical
+  settings across directions, and bf16 when on the GPU (the kernels are
+  bf16-only; other GPU dtypes keep their own numerics on the loop path).
+  """
+  c0 = cells[0]
+  for cell in cells:
+    cp = cell.p
+    if type(cell) is not LSTMCellSimpleExt:
+      return False
+    if (cp.couple_input_forget_gates or cell._proj or
+        not cp.output_nonlinearity or cp.zo_prob != 0.0):
+      return False
+    if cell._hidden % 32 != 0:
+      return False
+    if cp.cell_value_cap is not None and cp.cell_value_cap <= 0:
+      return False
+    if (cell._hidden != c0._hidden or
+        cp.num_input_nodes != c0.p.num_input_nodes or
+        cp.forget_gate_bias != c0.p.forget_gate_bias or
+        cp.cell_value_cap != c0.p.cell_value_cap or
+        cp.enable_lstm_bias != c0.p.enable_lstm_bias):
+      return False
+  if inputs.is_cuda and inputs.dtype != torch.bfloat16:
+    return False
+  return True
+
+
+def _FusedScan(cells, thetas, reverse_flags, inputs: torch.Tensor,
+               paddings: Optional[torch.Tensor]):
+  """inputs [B,T,Din] -> (m, c) each [D,T,B,H] via ops.lstm_scan."""
+  from lingvo_amd.ops import lstm_scan as scan_ops
+  cp = cells[0].p
+  b, t, _ = inputs.shape
+  x = inputs.transpose(0, 1)
+  pad = (paddings.transpose(0, 1) if paddings is not None else
+         torch.zeros(t, b, dtype=inputs.dtype, device=inputs.device))
+  return scan_ops.lstm_scan(
+      x, [th.wm for th in thetas],
+      [th.b if cp.enable_lstm_bias else None for th in thetas], pad,
+      cp.forget_gate_bias,
+      cp.cell_value_cap if cp.cell_value_cap is not None else 0.0,
+      reverse_flags)
+
+
 class LstmFRNN(BaseLayer):
   """FRNN over LSTMCellSimpleExt with hoisted input projection
   (reference lstm_frnn_layer.py LSTMFRNN). API mirrors
@@ -88,6 +141,9 @@ class LstmFRNN(BaseLayer):
     p.Define('cell', LSTMCellSimpleExt.Params(), 'Cell params.')
     p.Define('reverse', False, 'Scan right-to-left.')
     p.Define('remat', False, 'Recompute cells in backward.')
+    p.Define('fused_scan', False,
+             'Run the whole scan through ops.lstm_scan (one launch per '
+             'step) when the configuration is eligible.')
     return p
 
   def __init__(self, params):
@@ -103,6 +159,12 @@ class LstmFRNN(BaseLayer):
             state0: Optional[NestedMap] = None):
     p = self.p
     b, t, _ = inputs.shape
+    if (p.fused_scan and state0 is None and not p.remat and
+        _FusedScanEligible([self.cell], inputs)):
+      m, c = _FusedScan([self.cell], [theta.cell], (p.reverse,), inputs,
+                        paddings)
+      last = 0 if p.reverse else t - 1
+      return m[0].transpose(0, 1), NestedMap(c=c[0, last], m=m[0, last])
     x = inputs.transpose(0, 1)
     pad = (paddings.transpose(0, 1).unsqueeze(-1).to(inputs.dtype)
            if paddings is not None else torch.zeros(
@@ -137,15 +199,25 @@ class BidirectionalLstmFRNN(BaseLayer):
     p = super().Params()
     p.Define('fwd', LSTMCellSimpleExt.Params(), 'Forward cell.')
     p.Define('bak', LSTMCellSimpleExt.Params(), 'Backward cell.')
+    p.Define('fused_scan', False,
+             'Run both directions through ops.lstm_scan in the same '
+             'launches (D=2) when the configuration is eligible.')
     return p
 
   def __init__(self, params):
     super().__init__(params)
-    self.CreateChild('fwd_rnn', LstmFRNN.Params().Set(cell=self.p.fwd))
-    self.CreateChild('bak_rnn', LstmFRNN.Params().Set(cell=self.p.bak,
-                                                      reverse=True))
+    fused = self.p.fused_scan
+    self.CreateChild('fwd_rnn', LstmFRNN.Params().Set(
+        cell=self.p.fwd, fused_scan=fused))
+    self.CreateChild('bak_rnn', LstmFRNN.Params().Set(
+        cell=self.p.bak, reverse=True, fused_scan=fused))
 
   def FProp(self, theta, inputs, paddings=None):
+    cells = [self.fwd_rnn.cell, self.bak_rnn.cell]
+    if self.p.fused_scan and _FusedScanEligible(cells, inputs):
+      m, _ = _FusedScan(cells, [theta.fwd_rnn.cell, theta.bak_rnn.cell],
+                        (False, True), inputs, paddings)
+      return torch.cat([m[0], m[1]], dim=-1).transpose(0, 1)
     out_f, _ = self.fwd_rnn.FProp(theta.fwd_rnn, inputs, paddings)
     out_b, _ = self.bak_rnn.FProp(theta.bak_rnn, inputs, paddings)
     return torch.cat([out_f, out_b], dim=-1)

@@ -142,6 +142,9 @@ class LasEncoder(BaseLayer):
     p.Define('num_lstm_layers', 4, 'biLSTM layers.')
     p.Define('dropout_prob', 0.0, 'Inter-layer dropout.')
     p.Define('subsample_channels', 32, 'Frontend conv channels.')
+    p.Define('fused_blstm_scan', False,
+             'biLSTM layers use the fused scan (ops.lstm_scan): one HIP '
+             'launch per timestep for both directions.')
     return p
 
   def __init__(self, params):
@@ -160,7 +163,8 @@ class LasEncoder(BaseLayer):
       cell = lstm_frnn_layer.LSTMCellSimpleExt.Params().Set(
           num_input_nodes=p.model_dim, num_output_nodes=half)
       layer_ps.append(lstm_frnn_layer.BidirectionalLstmFRNN.Params().Set(
-          name=f'blstm_{i}', fwd=cell.Copy(), bak=cell.Copy()))
+          name=f'blstm_{i}', fwd=cell.Copy(), bak=cell.Copy(),
+          fused_scan=p.fused_blstm_scan))
     self.CreateChildren('rnn', layer_ps)
 
   def FProp(self, theta: NestedMap, src_inputs: torch.Tensor,

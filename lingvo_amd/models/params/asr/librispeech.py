@@ -101,6 +101,17 @@ class Librispeech960Base(Librispeech960WpmConformerL):
 
 
 @registry.RegisterSingleTaskModel
+class Librispeech960BaseFusedScan(Librispeech960Base):
+  """Librispeech960Base with the encoder biLSTMs on the fused scan
+  (ops.lstm_scan). Same variables, so checkpoints interchange."""
+
+  def Task(self):
+    p = super().Task()
+    p.encoder.fused_blstm_scan = True
+    return p
+
+
+@registry.RegisterSingleTaskModel
 class Librispeech960BaseGrapheme(Librispeech960Base):
   """Grapheme-target LAS (reference librispeech.py:156)."""
 

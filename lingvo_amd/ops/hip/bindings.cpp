@@ -127,6 +127,19 @@ std::vector<torch::Tensor> attend_bwd(torch::Tensor dctx,
                                       torch::Tensor enc, torch::Tensor denc,
                                       double scale);
 
+// lstm_scan.hip
+void lstm_scan_fwd(torch::Tensor gates, torch::Tensor c, torch::Tensor m,
+                   torch::Tensor pad, torch::Tensor wmt, int64_t rev_mask,
+                   double fgb, double cap, int64_t s_begin, int64_t s_end,
+                   int64_t rows_per_block);
+void lstm_scan_bwd(torch::Tensor gates, torch::Tensor c, torch::Tensor pad,
+                   torch::Tensor wm, c10::optional<torch::Tensor> dm_out,
+                   c10::optional<torch::Tensor> dc_out,
+                   torch::Tensor dgates, torch::Tensor dc_carry,
+                   torch::Tensor dm_pass, int64_t rev_mask, double fgb,
+                   double cap, int64_t s_begin, int64_t s_end,
+                   int64_t rows_per_block);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   RegisterInputPipeline(m);
   RegisterWpmTokenizer(m);
@@ -156,6 +169,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Small-M MFMA GEMM (decode-step projections)");
   m.def("attend_fwd", &attend_fwd, "Fused dot-attention step fwd");
   m.def("attend_bwd", &attend_bwd, "Fused dot-attention step bwd");
+  m.def("lstm_scan_fwd", &lstm_scan_fwd,
+        "Fused LSTM scan forward: one launch per step, all directions");
+  m.def("lstm_scan_bwd", &lstm_scan_bwd,
+        "Fused LSTM scan backward: one launch per step, all directions");
   m.def("s2d_fwd", &s2d_fwd, "Space-to-depth + pad (conv frontend)");
   m.def("topk_rows", &topk_rows, "Row-wise top-k (beam pruning, K12)");
   m.def("s2d_inv", &s2d_inv, "Inverse space-to-depth");
