@@ -276,6 +276,12 @@ class AsrDecoder(BaseLayer):
 
     fgb = self.rnns[0].p.forget_gate_bias
     use_fused = enc.is_cuda and dt == torch.bfloat16
+    # Shapes the las_decoder.hip kernels support (K % 32 of every small-M
+    # GEMM, D <= 2048 of the attention step).
+    fused_shape_ok = (h % 32 == 0 and p.source_dim % 32 == 0 and
+                      p.source_dim <= 2048)
+    if use_fused and not fused_shape_ok:
+      return self._LoopPredictions(theta, enc, enc_paddings, targets)
 
     if use_fused:
       # Whole-recurrence fused path (ops/las_decoder.py): per-step

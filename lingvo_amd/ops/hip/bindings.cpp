@@ -126,6 +126,8 @@ std::vector<torch::Tensor> attend_bwd(torch::Tensor dctx,
                                       torch::Tensor probs, torch::Tensor q,
                                       torch::Tensor enc, torch::Tensor denc,
                                       double scale);
+int64_t attend_lds_limit();
+int64_t attend_lds_bytes(int64_t s, int64_t d, bool bwd);
 
 // lstm_scan.hip
 void lstm_scan_fwd(torch::Tensor gates, torch::Tensor c, torch::Tensor m,
@@ -169,6 +171,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Small-M MFMA GEMM (decode-step projections)");
   m.def("attend_fwd", &attend_fwd, "Fused dot-attention step fwd");
   m.def("attend_bwd", &attend_bwd, "Fused dot-attention step bwd");
+  m.def("attend_lds_limit", &attend_lds_limit,
+        "Dynamic LDS bytes an attend_* launch may ask for on this device");
+  m.def("attend_lds_bytes", &attend_lds_bytes,
+        "Dynamic LDS bytes attend_fwd/attend_bwd ask for at (S, D)");
   m.def("lstm_scan_fwd", &lstm_scan_fwd,
         "Fused LSTM scan forward: one launch per step, all directions");
   m.def("lstm_scan_bwd", &lstm_scan_bwd,

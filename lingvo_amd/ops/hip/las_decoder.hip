@@ -18,6 +18,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <atomic>
+
 #include "common.h"
 #include "mfma.h"
 
@@ -28,9 +30,9 @@ namespace {
 //   pre_mode: 0 none, 1 row-vector [N], 2 full matrix [M,N],
 //             3 accumulate into existing out
 // A row-major [M, K] (contiguous), Wt row-major [N, ldw] with the
-// mathematical W^T in its first K columns. M <= 128, K % 32 == 0.
-// Grid: (ceil(N/16)); block 256 = 4 waves; wave w owns m-tiles
-// {2w, 2w+1} (rows 32w .. 32w+31).
+// mathematical W^T in its first K columns. K % 32 == 0.
+// Grid: (ceil(N/16), ceil(M/128)); block 256 = 4 waves; wave w owns a
+// quarter of K for all 8 m-tiles of its 128-row m-block.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void smallm_gemm_kernel(
     const unsigned short* __restrict__ a, const unsigned short* __restrict__ wt,
@@ -427,29 +429,95 @@ __global__ __launch_bounds__(256) void attend_bwd_kernel(
 
 // ---------------------------------------------------------------------------
 // Host wrappers
+//
+// Every shape, dtype and resource condition a kernel relies on is checked
+// here, before any allocation and before the launch, so a bad call raises
+// and leaves its output buffers untouched.
 // ---------------------------------------------------------------------------
+
+namespace {
+
+// Largest dynamic LDS request a launch on the current device accepts.
+// Queried once per device: the wrappers run several times per decoder step.
+size_t lds_limit_bytes() {
+  constexpr int kMaxDevices = 64;
+  static std::atomic<int> cached[kMaxDevices];  // zero-initialised
+  int dev = 0;
+  LV_CHECK_HIP(hipGetDevice(&dev));
+  const bool cacheable = dev >= 0 && dev < kMaxDevices;
+  int limit = cacheable ? cached[dev].load(std::memory_order_relaxed) : 0;
+  if (limit == 0) {
+    LV_CHECK_HIP(hipDeviceGetAttribute(
+        &limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    if (cacheable) cached[dev].store(limit, std::memory_order_relaxed);
+  }
+  return (size_t)limit;
+}
+
+constexpr int64_t kAttendMaxD = 4 * WAVE_SIZE * 8;  // MAXDV register slices
+
+size_t attend_fwd_lds(int64_t s, int64_t d) {
+  return (size_t)d * 2 + (size_t)s * 4 + (size_t)4 * d * 4 + 16;
+}
+
+size_t attend_bwd_lds(int64_t s, int64_t d) {
+  return (size_t)d * 4 + (size_t)s * 4 + (size_t)4 * d * 4 + 16;
+}
+
+bool cuda_contig(const torch::Tensor& t, torch::ScalarType st) {
+  return t.is_cuda() && t.is_contiguous() && t.scalar_type() == st;
+}
+
+// Checks shared by attend_fwd (q, enc, pad) and attend_bwd (q, enc).
+void check_attend_q_enc(const torch::Tensor& q, const torch::Tensor& enc) {
+  TORCH_CHECK(cuda_contig(q, torch::kBFloat16) && q.dim() == 2,
+              "q must be CUDA contiguous bf16 [B,D]");
+  TORCH_CHECK(cuda_contig(enc, torch::kBFloat16) && enc.dim() == 3,
+              "enc must be CUDA contiguous bf16 [B,S,D]");
+  const int64_t b = q.size(0), d = q.size(1);
+  TORCH_CHECK(b >= 1 && enc.size(0) == b && enc.size(2) == d,
+              "enc must be [B,S,D] for q [B,D]");
+  TORCH_CHECK(enc.size(1) >= 1, "S >= 1");
+  TORCH_CHECK(d >= 8 && d % 8 == 0, "D % 8 == 0");
+  TORCH_CHECK(d <= kAttendMaxD, "D <= 2048");
+}
+
+}  // namespace
 
 void smallm_gemm(torch::Tensor a, torch::Tensor wt,
                  c10::optional<torch::Tensor> pre, torch::Tensor out,
                  int64_t k, int64_t wt_col0, double alpha,
                  int64_t pre_mode) {
-  TORCH_CHECK(a.is_cuda() && a.is_contiguous() &&
-              a.scalar_type() == torch::kBFloat16, "a bf16 contig");
-  TORCH_CHECK(wt.is_cuda() && wt.is_contiguous() &&
-              wt.scalar_type() == torch::kBFloat16, "wt bf16 contig");
-  TORCH_CHECK(out.is_contiguous() && out.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(cuda_contig(a, torch::kBFloat16) && a.dim() == 2,
+              "a must be CUDA contiguous bf16 [M,K]");
+  TORCH_CHECK(cuda_contig(wt, torch::kBFloat16) && wt.dim() == 2,
+              "wt must be CUDA contiguous bf16 [>=N,ldw]");
+  TORCH_CHECK(cuda_contig(out, torch::kBFloat16) && out.dim() == 2,
+              "out must be CUDA contiguous bf16 [M,N]");
+  TORCH_CHECK(out.size(0) == a.size(0), "out must have M rows");
   const int m = a.size(0);
   const int n = out.size(1);
-  TORCH_CHECK(a.size(1) >= k && k % 32 == 0, "K%32");
+  TORCH_CHECK(m >= 1 && n >= 1, "M, N >= 1");
+  TORCH_CHECK(k >= 32 && k % 32 == 0, "K%32");
   TORCH_CHECK(k == a.size(1), "a must be [M,K] exactly");
 
   TORCH_CHECK(wt.size(0) >= n, "wt rows >= N");
   const long ldw = wt.size(1);
-  TORCH_CHECK(wt_col0 + k <= ldw, "wt K slice OOB");
+  TORCH_CHECK(wt_col0 >= 0 && wt_col0 + k <= ldw, "wt K slice OOB");
+  // 16-byte bf16x8 loads of Wt rows.
+  TORCH_CHECK(ldw % 8 == 0 && wt_col0 % 8 == 0,
+              "ldw % 8 == 0 and wt_col0 % 8 == 0");
+  TORCH_CHECK(pre_mode >= 0 && pre_mode <= 3, "pre_mode in 0..3");
   const unsigned short* prep = nullptr;
   if (pre_mode == 1 || pre_mode == 2) {
-    TORCH_CHECK(pre.has_value() && pre->is_contiguous() &&
-                pre->scalar_type() == torch::kBFloat16);
+    TORCH_CHECK(pre.has_value() && cuda_contig(*pre, torch::kBFloat16),
+                "pre must be CUDA contiguous bf16");
+    if (pre_mode == 1) {
+      TORCH_CHECK(pre->numel() == n, "mode 1: pre must have N elements");
+    } else {
+      TORCH_CHECK(pre->dim() == 2 && pre->size(0) == m && pre->size(1) == n,
+                  "mode 2: pre must be [M,N]");
+    }
     prep = (const unsigned short*)pre->data_ptr();
   }
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -459,21 +527,22 @@ void smallm_gemm(torch::Tensor a, torch::Tensor wt,
                      (const unsigned short*)wt.data_ptr() + wt_col0,
                      prep, (unsigned short*)out.data_ptr(), m, n, (int)k,
                      ldw, (float)alpha, (int)pre_mode);
+  LV_CHECK_HIP(hipGetLastError());
 }
 
 std::vector<torch::Tensor> attend_fwd(torch::Tensor q, torch::Tensor enc,
                                       torch::Tensor pad, double scale) {
-  TORCH_CHECK(q.is_cuda() && q.is_contiguous() &&
-              q.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(enc.is_contiguous() &&
-              enc.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(pad.is_contiguous() && pad.scalar_type() == torch::kFloat32);
+  check_attend_q_enc(q, enc);
   const int b = q.size(0), d = q.size(1);
   const int s = enc.size(1);
-  TORCH_CHECK(d % 8 == 0, "D % 8 == 0");
+  TORCH_CHECK(cuda_contig(pad, torch::kFloat32) && pad.dim() == 2 &&
+              pad.size(0) == b && pad.size(1) == s,
+              "pad must be CUDA contiguous fp32 [B,S]");
+  const size_t shmem = attend_fwd_lds(s, d);
+  TORCH_CHECK(shmem <= lds_limit_bytes(), "attend_fwd: S=", s, " D=", d,
+              " needs ", shmem, " bytes of LDS, over the device limit");
   auto probs = torch::empty({b, s}, q.options().dtype(torch::kFloat32));
   auto ctx = torch::empty({b, d}, q.options());
-  size_t shmem = (size_t)d * 2 + (size_t)s * 4 + (size_t)4 * d * 4 + 16;
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(attend_fwd_kernel, dim3(b), dim3(256), shmem, stream,
                      (const unsigned short*)q.data_ptr(),
@@ -481,6 +550,7 @@ std::vector<torch::Tensor> attend_fwd(torch::Tensor q, torch::Tensor enc,
                      pad.data_ptr<float>(), probs.data_ptr<float>(),
                      (unsigned short*)ctx.data_ptr(), b, s, d,
                      (float)scale);
+  LV_CHECK_HIP(hipGetLastError());
   return {probs, ctx};
 }
 
@@ -488,13 +558,24 @@ std::vector<torch::Tensor> attend_bwd(torch::Tensor dctx,
                                       torch::Tensor probs, torch::Tensor q,
                                       torch::Tensor enc, torch::Tensor denc,
                                       double scale) {
+  check_attend_q_enc(q, enc);
   const int b = q.size(0), d = q.size(1);
   const int s = enc.size(1);
-  TORCH_CHECK(denc.is_contiguous() &&
-              denc.scalar_type() == torch::kFloat32);
+  // dctx may arrive in any float type; it is cast to bf16 below.
+  TORCH_CHECK(dctx.is_cuda() && dctx.is_floating_point() &&
+              dctx.dim() == 2 && dctx.size(0) == b && dctx.size(1) == d,
+              "dctx must be a CUDA float tensor [B,D]");
+  TORCH_CHECK(cuda_contig(probs, torch::kFloat32) && probs.dim() == 2 &&
+              probs.size(0) == b && probs.size(1) == s,
+              "probs must be CUDA contiguous fp32 [B,S]");
+  TORCH_CHECK(cuda_contig(denc, torch::kFloat32) && denc.dim() == 3 &&
+              denc.size(0) == b && denc.size(1) == s && denc.size(2) == d,
+              "denc must be CUDA contiguous fp32 [B,S,D]");
+  const size_t shmem = attend_bwd_lds(s, d);
+  TORCH_CHECK(shmem <= lds_limit_bytes(), "attend_bwd: S=", s, " D=", d,
+              " needs ", shmem, " bytes of LDS, over the device limit");
   auto dctx_c = dctx.to(torch::kBFloat16).contiguous();
   auto dq = torch::empty({b, d}, q.options());
-  size_t shmem = (size_t)d * 4 + (size_t)s * 4 + (size_t)4 * d * 4 + 16;
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(attend_bwd_kernel, dim3(b), dim3(256), shmem, stream,
                      (const unsigned short*)dctx_c.data_ptr(),
@@ -503,5 +584,14 @@ std::vector<torch::Tensor> attend_bwd(torch::Tensor dctx,
                      (const unsigned short*)enc.data_ptr(),
                      (unsigned short*)dq.data_ptr(),
                      denc.data_ptr<float>(), b, s, d, (float)scale);
+  LV_CHECK_HIP(hipGetLastError());
   return {dq};
+}
+
+// Dynamic-LDS limit the attend_* launches are held to on the current
+// device, and the bytes a call with these S, D asks for.
+int64_t attend_lds_limit() { return (int64_t)lds_limit_bytes(); }
+
+int64_t attend_lds_bytes(int64_t s, int64_t d, bool bwd) {
+  return (int64_t)(bwd ? attend_bwd_lds(s, d) : attend_fwd_lds(s, d));
 }
