@@ -422,6 +422,108 @@ class AsrDecoder(BaseLayer):
     return torch.stack(out, dim=1)
 
 
+class CtcDecoder(BaseLayer):
+  """CTC head: one projection of the encoder outputs to the vocabulary,
+  trained with the CTC loss (ops.ctc) and decoded frame-synchronously.
+  Has the four methods AsrModel and StreamingRecognizer reach a decoder
+  through, with AsrDecoder's signatures."""
+
+  @classmethod
+  def Params(cls):
+    p = super().Params()
+    p.Define('vocab_size', 1024, 'Output vocab, blank included.')
+    p.Define('source_dim', 512, 'Encoder output dim.')
+    p.Define('blank_id', 0, 'Id of the CTC blank.')
+    p.Define('dropout_prob', 0.1, 'Dropout on the encoder outputs.')
+    p.Define('ctc_impl', 'auto',
+             "ops.ctc.ctc_loss impl: 'auto' (HIP kernels on GPU, torch twin "
+             "on CPU) or 'torch' (torch.nn.functional.ctc_loss).")
+    return p
+
+  def __init__(self, params):
+    super().__init__(params)
+    p = self.p
+    assert 0 <= p.blank_id < p.vocab_size
+    self.CreateChild('softmax', lingvo_layers.SimpleFullSoftmax.Params().Set(
+        input_dim=p.source_dim, num_classes=p.vocab_size))
+
+  def _Logits(self, theta: NestedMap, enc: torch.Tensor) -> torch.Tensor:
+    return self.softmax.Logits(theta.softmax, enc.to(self.fprop_dtype))
+
+  def ComputePredictions(self, theta: NestedMap, enc: torch.Tensor,
+                         enc_paddings: torch.Tensor,
+                         targets: NestedMap) -> NestedMap:
+    del targets  # frame-synchronous: no teacher forcing
+    if self.p.dropout_prob and not self.do_eval:
+      enc = py_utils.DeterministicDropout(enc, 1.0 - self.p.dropout_prob)
+    return NestedMap(logits=self._Logits(theta, enc), paddings=enc_paddings)
+
+  def ComputeLoss(self, theta: NestedMap, predictions: NestedMap,
+                  targets: NestedMap):
+    """Mean nll over the utterances that have an alignment. No host sync:
+    the whole loss captures into a hipGraph."""
+    from lingvo_amd.ops import ctc as ctc_ops
+    p = self.p
+    logits = predictions.logits
+    logit_lengths = py_utils.LengthsFromPaddings(predictions.paddings)
+    label_lengths = py_utils.LengthsFromPaddings(targets.paddings)
+    nll, valid = ctc_ops.ctc_loss(
+        logits.contiguous(), logit_lengths, targets.ids.long(),
+        label_lengths, blank_id=p.blank_id, impl=p.ctc_impl)
+    nll = nll.float()
+    valid = valid.float()
+    num_valid = valid.sum()
+    total = (nll * valid).sum()
+    num_labels = (label_lengths.float() * valid).sum()
+    metrics = NestedMap(
+        loss=(total / num_valid.clamp(min=1.0), num_valid),
+        log_pplx=(total.detach() / num_labels.clamp(min=1.0), num_labels),
+        ctc_valid_fraction=(valid.mean(),
+                            torch.tensor(float(valid.shape[0]))))
+    return metrics, NestedMap(per_example_xent=nll)
+
+  def GreedyDecode(self, theta: NestedMap, enc: torch.Tensor,
+                   enc_paddings: torch.Tensor, max_len: int = 0,
+                   sos_id: int = 1, eos_id: int = 2,
+                   fusion=None) -> torch.Tensor:
+    """Best-path decode: per-frame argmax over the unpadded frames, repeats
+    collapsed, blanks dropped, left-packed into [B, T'] long padded with 0.
+    Static width and no host sync. max_len/sos_id/eos_id are accepted for
+    AsrDecoder's signature and unused."""
+    del max_len, sos_id, eos_id
+    if fusion is not None:
+      raise NotImplementedError(
+          'CtcDecoder.GreedyDecode: LM shallow fusion is not built for CTC')
+    blank = self.p.blank_id
+    b, t = enc.shape[0], enc.shape[1]
+    if t == 0:
+      return torch.zeros(b, 0, dtype=torch.long, device=enc.device)
+    ids = self._Logits(theta, enc).argmax(-1)  # [B, T']
+    keep = enc_paddings < 0.5
+    # The previous unpadded frame's id (-1 before the first one).
+    pos = torch.arange(t, device=enc.device)[None, :].expand(b, t)
+    last = torch.cummax(torch.where(keep, pos, torch.full_like(pos, -1)),
+                        dim=1).values
+    prev_pos = torch.cat([torch.full_like(last[:, :1], -1), last[:, :-1]],
+                         dim=1)
+    prev = torch.where(prev_pos >= 0, ids.gather(1, prev_pos.clamp(min=0)),
+                       torch.full_like(ids, -1))
+    emit = keep & (ids != blank) & (ids != prev)
+    slot = torch.where(emit, torch.cumsum(emit.long(), dim=1) - 1,
+                       torch.full_like(pos, t))  # dropped frames -> column T'
+    out = torch.zeros(b, t + 1, dtype=torch.long, device=enc.device)
+    out.scatter_(1, slot, torch.where(emit, ids, torch.zeros_like(ids)))
+    return out[:, :t].contiguous()
+
+  def BeamSearchDecode(self, theta: NestedMap, enc: torch.Tensor,
+                       enc_paddings: torch.Tensor, num_hyps: int = 8,
+                       max_steps: int = 100,
+                       length_norm: float = 0.0) -> NestedMap:
+    raise NotImplementedError(
+        'CtcDecoder.BeamSearchDecode: CTC prefix beam search is not built; '
+        'use GreedyDecode (decode_num_hyps=1)')
+
+
 class ShallowFusion:
   """LM shallow fusion for decoding (reference tasks/asr/fusion.py):
   combined score = log p_am + weight * log p_lm, with the LM advanced
@@ -461,12 +563,24 @@ class AsrModel(BaseTask):
     p.Define('decoder', AsrDecoder.Params(), 'Decoder params.')
     p.Define('decode_num_hyps', 1,
              'Beam width for Decode(); 1 = greedy.')
+    p.Define('ctc_weight', 0.0,
+             'If > 0, joint CTC/attention training: an auxiliary '
+             'CtcDecoder over the encoder outputs and loss = '
+             '(1 - w) * decoder loss + w * CTC loss.')
+    p.Define('aux_ctc', CtcDecoder.Params(),
+             'Template of the auxiliary CTC head (ctc_weight > 0); '
+             'vocab_size and source_dim follow the decoder.')
     return p
 
   def __init__(self, params):
     super().__init__(params)
-    self.CreateChild('encoder', self.p.encoder)
-    self.CreateChild('decoder', self.p.decoder)
+    p = self.p
+    self.CreateChild('encoder', p.encoder)
+    self.CreateChild('decoder', p.decoder)
+    assert 0.0 <= p.ctc_weight <= 1.0
+    if p.ctc_weight > 0:
+      self.CreateChild('aux_ctc', p.aux_ctc.Copy().Set(
+          vocab_size=p.decoder.vocab_size, source_dim=p.decoder.source_dim))
 
   def ComputePredictions(self, theta: NestedMap,
                          input_batch: NestedMap) -> NestedMap:
@@ -477,12 +591,26 @@ class AsrModel(BaseTask):
                                             input_batch.tgt)
     preds.encoder_outputs = enc
     preds.encoder_paddings = enc_pad
+    if self.p.ctc_weight > 0:
+      preds.aux_ctc = self.aux_ctc.ComputePredictions(
+          theta.aux_ctc, enc, enc_pad, input_batch.tgt)
     return preds
 
   def ComputeLoss(self, theta: NestedMap, predictions: NestedMap,
                   input_batch: NestedMap):
     metrics, per_example = self.decoder.ComputeLoss(
         theta.decoder, predictions, input_batch.tgt)
+    w = self.p.ctc_weight
+    if w > 0:
+      ctc_metrics, ctc_per_example = self.aux_ctc.ComputeLoss(
+          theta.aux_ctc, predictions.aux_ctc, input_batch.tgt)
+      att_loss, att_weight = metrics.loss
+      ctc_loss = ctc_metrics.loss[0]
+      metrics.att_loss = (att_loss.detach(), att_weight)
+      metrics.ctc_loss = (ctc_loss.detach(), ctc_metrics.loss[1])
+      metrics.ctc_valid_fraction = ctc_metrics.ctc_valid_fraction
+      metrics.loss = ((1.0 - w) * att_loss + w * ctc_loss, att_weight)
+      per_example.per_example_ctc = ctc_per_example.per_example_xent
     b = input_batch.src.src_inputs.shape[0]
     metrics.num_samples_in_batch = (
         torch.tensor(float(b)), torch.ones(()))

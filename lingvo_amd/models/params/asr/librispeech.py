@@ -133,3 +133,46 @@ class Librispeech960Wpm(Librispeech960Base):
     p.name = 'librispeech_las_wpm'
     p.decoder.Set(vocab_size=self.VOCAB, emb_dim=96)
     return p
+
+
+def _CtcHead(task_p):
+  """Replaces the attention decoder of `task_p` with a CTC head of the
+  same vocabulary over the same encoder outputs."""
+  old = task_p.decoder
+  task_p.decoder = asr_model.CtcDecoder.Params().Set(
+      vocab_size=old.vocab_size, source_dim=old.source_dim,
+      dropout_prob=old.dropout_prob)
+  return task_p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960WpmConformerLCtc(Librispeech960WpmConformerL):
+  """CTC-only Conformer-L: the north-star encoder, learner and input with
+  a CtcDecoder (frame-synchronous decode, no decoder recurrence)."""
+
+  def Task(self):
+    p = _CtcHead(super().Task())
+    p.name = 'librispeech_conformer_l_ctc'
+    return p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960ConformerSCtc(Librispeech960ConformerS):
+  """CTC-only Conformer-S: quick tests."""
+
+  def Task(self):
+    p = _CtcHead(super().Task())
+    p.name = 'librispeech_conformer_s_ctc'
+    return p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960WpmConformerLJointCtc(Librispeech960WpmConformerL):
+  """Joint CTC/attention Conformer-L: the attention decoder plus an
+  auxiliary CTC head on the encoder, loss = 0.7 attention + 0.3 CTC."""
+
+  def Task(self):
+    p = super().Task()
+    p.name = 'librispeech_conformer_l_joint_ctc'
+    p.ctc_weight = 0.3
+    return p

@@ -142,6 +142,20 @@ void lstm_scan_bwd(torch::Tensor gates, torch::Tensor c, torch::Tensor pad,
                    double cap, int64_t s_begin, int64_t s_end,
                    int64_t rows_per_block);
 
+// ctc.hip
+std::vector<torch::Tensor> ctc_fwd(torch::Tensor logits,
+                                   torch::Tensor logit_lengths,
+                                   torch::Tensor labels,
+                                   torch::Tensor label_lengths,
+                                   int64_t blank);
+torch::Tensor ctc_bwd(torch::Tensor logits, torch::Tensor logit_lengths,
+                      torch::Tensor labels, torch::Tensor label_lengths,
+                      torch::Tensor lse, torch::Tensor emis,
+                      torch::Tensor alpha, torch::Tensor beta,
+                      torch::Tensor nll, torch::Tensor valid,
+                      torch::Tensor gout, int64_t blank);
+int64_t ctc_max_label_len();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   RegisterInputPipeline(m);
   RegisterWpmTokenizer(m);
@@ -179,6 +193,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused LSTM scan forward: one launch per step, all directions");
   m.def("lstm_scan_bwd", &lstm_scan_bwd,
         "Fused LSTM scan backward: one launch per step, all directions");
+  m.def("ctc_fwd", &ctc_fwd,
+        "CTC loss forward: nll, valid and the backward's workspaces");
+  m.def("ctc_bwd", &ctc_bwd, "CTC loss backward: dlogits");
+  m.def("ctc_max_label_len", &ctc_max_label_len,
+        "Largest label width L the CTC kernels support");
   m.def("s2d_fwd", &s2d_fwd, "Space-to-depth + pad (conv frontend)");
   m.def("topk_rows", &topk_rows, "Row-wise top-k (beam pruning, K12)");
   m.def("s2d_inv", &s2d_inv, "Inverse space-to-depth");
