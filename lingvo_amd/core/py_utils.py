@@ -506,6 +506,71 @@ def MatmulBias(x: torch.Tensor, w: torch.Tensor,
   return out.reshape(*shape[:-1], w.shape[-1])
 
 
+# --------------------------------------------------------------------------
+# Glue fusion switch
+# --------------------------------------------------------------------------
+# On (default): self-attention reads q/k/v straight out of the packed QKV
+# projection and writes one dQKV (flash_attn.flash_attention_packed), bias
+# gradients come out of the dropout backward kernel (MatmulBiasDropout /
+# MatmulBiasDropoutAdd), the attention output padding rides in the
+# residual dropout kernel, and the residual gradient of a pre-LN block is
+# added inside the LayerNorm backward kernel (LayerNorm.FPropWithResidual).
+# Off: the unfused op sequence (split + copies + cat, addmm, dropout,
+# autograd's bias sum and gradient add), which the tests use as their
+# yardstick. Forward values are the same either way.
+def GlueFusion() -> bool:
+  from lingvo_amd.ops import fusion
+  return fusion.enabled()
+
+
+def SetGlueFusion(enabled: bool) -> bool:
+  """Sets the switch in-process; returns the previous value."""
+  from lingvo_amd.ops import fusion
+  return fusion.set_enabled(enabled)
+
+
+def _CanFuseLinearDropout(x, w, b, keep_prob) -> bool:
+  return (GlueFusion() and b is not None and keep_prob < 1.0 and
+          x.is_cuda and x.dtype == torch.bfloat16 and
+          w.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and
+          w.shape[-1] % 8 == 0 and x.numel() > 0)
+
+
+def MatmulBiasDropout(x: torch.Tensor, w: torch.Tensor,
+                      b: Optional[torch.Tensor], keep_prob: float,
+                      op_seed: Optional[int] = None,
+                      act: str = 'NONE') -> torch.Tensor:
+  """DeterministicDropout(MatmulBias(x, w, b), keep_prob, act=act). With
+  GlueFusion on GPU bf16 it is one autograd node whose dropout backward
+  kernel also yields db, so no separate pass re-reads dx for the bias
+  sum. Draws one step-seed pair, like DeterministicDropout."""
+  if _CanFuseLinearDropout(x, w, b, keep_prob):
+    from lingvo_amd.ops import dropout as dropout_ops
+    s1, _ = GenerateStepSeedPair(op_seed)
+    return dropout_ops.linear_dropout(x, w, b, keep_prob, s1, act=act)
+  return DeterministicDropout(MatmulBias(x, w, b), keep_prob, op_seed,
+                              act=act)
+
+
+def MatmulBiasDropoutAdd(x: torch.Tensor, w: torch.Tensor,
+                         b: Optional[torch.Tensor], keep_prob: float,
+                         residual: torch.Tensor,
+                         op_seed: Optional[int] = None, scale: float = 1.0,
+                         paddings: Optional[torch.Tensor] = None
+                         ) -> torch.Tensor:
+  """DeterministicDropoutAdd(MatmulBias(x, w, b), keep_prob, residual,
+  scale=scale, paddings=paddings), fused like MatmulBiasDropout."""
+  if _CanFuseLinearDropout(x, w, b, keep_prob) and \
+      residual.dtype == torch.bfloat16:
+    from lingvo_amd.ops import dropout as dropout_ops
+    s1, _ = GenerateStepSeedPair(op_seed)
+    return dropout_ops.linear_dropout(x, w, b, keep_prob, s1,
+                                      residual=residual, scale=scale,
+                                      paddings=paddings)
+  return DeterministicDropoutAdd(MatmulBias(x, w, b), keep_prob, residual,
+                                 op_seed, scale=scale, paddings=paddings)
+
+
 class Timer:
   """Accumulating wall-clock timer (reference py_utils.py:6890)."""
 

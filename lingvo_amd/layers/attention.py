@@ -96,29 +96,50 @@ class MultiHeadedAttention(BaseLayer):
     packed-input segment_ids [B, T] block cross-segment attention
     (reference packed-input segment mask, batch_major_attention.py)."""
     p = self.p
-    q, k, v = self._Project(theta, query_vec)
-    if p.use_rope:
-      q = self.rope.FProp(theta.rope, q)
-      k = self.rope.FProp(theta.rope, k)
-    klen = None
-    if paddings is not None and segment_ids is None:
-      klen = py_utils.LengthsFromPaddings(paddings).to(torch.int32)
-    bias = theta.rel_bias if p.rel_pos_bias else None
-    win_r = 0 if p.causal else p.right_context
-    out = flash_attn.flash_attention(
-        q, k, v, klen, bias, p.left_context, win_r, p.rel_pos_clip,
-        q_segment_ids=segment_ids, k_segment_ids=segment_ids)
-    if p.atten_dropout_prob and not self.do_eval:
-      # Dropout on the context vectors (prob-dropout approximation; the
-      # reference drops attention probs, batch_major_attention.py:1045).
-      out = py_utils.DeterministicDropout(out, 1.0 - p.atten_dropout_prob)
-    b, t = out.shape[0], out.shape[1]
-    ctx = out.reshape(b, t, self._n * self._h)
+    ctx = self.FPropContext(theta, query_vec, paddings, segment_ids)
     post = py_utils.MatmulBias(ctx, theta.post_w,
                                theta.post_b if p.use_bias else None)
     if paddings is not None:
       post = py_utils.ApplyPadding(paddings, post)
     return post
+
+  def FPropContext(self, theta: NestedMap, query_vec: torch.Tensor,
+                   paddings: Optional[torch.Tensor] = None,
+                   segment_ids: Optional[torch.Tensor] = None
+                   ) -> torch.Tensor:
+    """FProp up to the [B, T, N*H] context vectors, before the output
+    projection and its padding mask; for callers that fuse those two into
+    what follows (TransformerAttentionLayer)."""
+    p = self.p
+    klen = None
+    if paddings is not None and segment_ids is None:
+      klen = py_utils.LengthsFromPaddings(paddings).to(torch.int32)
+    bias = theta.rel_bias if p.rel_pos_bias else None
+    win_r = 0 if p.causal else p.right_context
+    if (py_utils.GlueFusion() and not p.use_rope and self._n == self._nkv
+        and query_vec.is_cuda and query_vec.dtype == torch.bfloat16 and
+        theta.qkv_w.dtype == torch.bfloat16):
+      # The kernels read q/k/v out of the packed projection and write one
+      # dQKV: no split copies forward, no cat backward.
+      qkv = py_utils.MatmulBias(query_vec, theta.qkv_w,
+                                theta.qkv_b if p.use_bias else None)
+      out = flash_attn.flash_attention_packed(
+          qkv, self._n, klen, bias, p.left_context, win_r, p.rel_pos_clip,
+          q_segment_ids=segment_ids, k_segment_ids=segment_ids)
+    else:
+      q, k, v = self._Project(theta, query_vec)
+      if p.use_rope:
+        q = self.rope.FProp(theta.rope, q)
+        k = self.rope.FProp(theta.rope, k)
+      out = flash_attn.flash_attention(
+          q, k, v, klen, bias, p.left_context, win_r, p.rel_pos_clip,
+          q_segment_ids=segment_ids, k_segment_ids=segment_ids)
+    if p.atten_dropout_prob and not self.do_eval:
+      # Dropout on the context vectors (prob-dropout approximation; the
+      # reference drops attention probs, batch_major_attention.py:1045).
+      out = py_utils.DeterministicDropout(out, 1.0 - p.atten_dropout_prob)
+    b, t = out.shape[0], out.shape[1]
+    return out.reshape(b, t, self._n * self._h)
 
   def _NoRope(self):
     if self.p.use_rope:

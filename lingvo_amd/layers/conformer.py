@@ -69,7 +69,7 @@ class LConvLayer(BaseLayer):
   def FProp(self, theta: NestedMap, inputs: torch.Tensor,
             paddings: Optional[torch.Tensor] = None) -> torch.Tensor:
     p = self.p
-    x = self.ln.FProp(theta.ln, inputs)
+    x, residual = transformer_lib.PreLn(self.ln, theta.ln, inputs)
     x = py_utils.MatmulBias(x, theta.pw1_w, theta.pw1_b)
     x = F.glu(x, dim=-1)  # fused GLU (single kernel fwd + bwd)
     if paddings is not None:
@@ -87,14 +87,16 @@ class LConvLayer(BaseLayer):
     else:
       x = self.norm.FProp(theta.norm, x, paddings)
       x = F.silu(x)
-    x = py_utils.MatmulBias(x, theta.pw2_w, theta.pw2_b)
     if p.dropout_prob and not self.do_eval:
-      # padding mask folds into the dropout kernel's elementwise pass.
-      return py_utils.DeterministicDropoutAdd(x, 1.0 - p.dropout_prob,
-                                              inputs, paddings=paddings)
+      # padding mask folds into the dropout kernel's elementwise pass,
+      # whose backward also yields the pw2 bias gradient.
+      return py_utils.MatmulBiasDropoutAdd(
+          x, theta.pw2_w, theta.pw2_b, 1.0 - p.dropout_prob, residual,
+          paddings=paddings)
+    x = py_utils.MatmulBias(x, theta.pw2_w, theta.pw2_b)
     if paddings is not None:
       x = py_utils.ApplyPadding(paddings, x)
-    return inputs + x
+    return residual + x
 
   def InitStreamState(self, batch: int, device, dtype) -> NestedMap:
     p = self.p

@@ -321,6 +321,19 @@ class LayerNorm(BaseLayer):
     out = out * (1.0 + theta.scale.float()) + theta.bias.float()
     return out.to(inputs.dtype)
 
+  def FPropWithResidual(self, theta: NestedMap, inputs: torch.Tensor):
+    """Returns (FProp(inputs), residual) for a pre-LN block. On the fused
+    GPU path `residual` is an alias of `inputs` whose gradient is added
+    inside the LN backward kernel (py_utils.GlueFusion); otherwise it is
+    `inputs` itself."""
+    p = self.p
+    if (py_utils.GlueFusion() and inputs.is_cuda and p.use_fused_layernorm
+        and inputs.dtype == torch.bfloat16 and inputs.requires_grad):
+      from lingvo_amd.ops import layer_norm as ln_ops
+      return ln_ops.layer_norm_with_residual(inputs, theta.scale, theta.bias,
+                                             p.epsilon)
+    return self.FProp(theta, inputs), inputs
+
 
 class RmsNorm(BaseLayer):
   """RMS normalization (no mean subtraction)."""

@@ -17,6 +17,15 @@ from lingvo_amd.layers import attention as attention_lib
 from lingvo_amd.layers import layers as lingvo_layers
 
 
+def PreLn(ln_layer, ln_theta, x):
+  """(LN(x), residual) for a pre-LN block. Where the norm layer offers
+  FPropWithResidual, `residual` carries x's value but routes its
+  gradient through the LN backward kernel (see py_utils.GlueFusion)."""
+  if hasattr(ln_layer, 'FPropWithResidual'):
+    return ln_layer.FPropWithResidual(ln_theta, x)
+  return ln_layer.FProp(ln_theta, x), x
+
+
 class TransformerAttentionLayer(BaseLayer):
   """Pre-LN self/cross attention block with residual."""
 
@@ -51,17 +60,30 @@ class TransformerAttentionLayer(BaseLayer):
             source_paddings: Optional[torch.Tensor] = None,
             segment_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     p = self.p
-    x = self.layer_norm.FProp(theta.layer_norm, query_vec)
+    x, residual = PreLn(self.layer_norm, theta.layer_norm, query_vec)
+    dropout = p.residual_dropout_prob and not self.do_eval
+    if (source_vecs is None and dropout and py_utils.GlueFusion() and
+        type(self.atten) is attention_lib.MultiHeadedAttention):
+      # The output projection, its padding mask and the residual dropout
+      # run as one node: db comes out of the dropout backward kernel and
+      # the mask costs no pass of its own. Subclasses that override FProp
+      # keep their own output path.
+      ctx = self.atten.FPropContext(theta.atten, x, paddings,
+                                    segment_ids=segment_ids)
+      return py_utils.MatmulBiasDropoutAdd(
+          ctx, theta.atten.post_w,
+          theta.atten.post_b if self.atten.p.use_bias else None,
+          1.0 - p.residual_dropout_prob, residual, paddings=paddings)
     if source_vecs is None:
       ctx = self.atten.FProp(theta.atten, x, paddings,
                              segment_ids=segment_ids)
     else:
       ctx = self.atten.FPropCross(theta.atten, x, source_vecs, source_vecs,
                                   source_paddings)
-    if p.residual_dropout_prob and not self.do_eval:
+    if dropout:
       return py_utils.DeterministicDropoutAdd(
-          ctx, 1.0 - p.residual_dropout_prob, query_vec)
-    return query_vec + ctx
+          ctx, 1.0 - p.residual_dropout_prob, residual)
+    return residual + ctx
 
   def InitStates(self, theta, batch, max_len, device, dtype=torch.bfloat16):
     return self.atten.InitStates(theta.atten, batch, max_len, device, dtype)
@@ -113,29 +135,31 @@ class TransformerFeedForwardLayer(BaseLayer):
   def FProp(self, theta: NestedMap, inputs: torch.Tensor,
             paddings: Optional[torch.Tensor] = None) -> torch.Tensor:
     p = self.p
-    x = self.layer_norm.FProp(theta.layer_norm, inputs)
-    h = py_utils.MatmulBias(x, theta.w1, theta.b1)
+    x, residual = PreLn(self.layer_norm, theta.layer_norm, inputs)
     if (p.relu_dropout_prob and not self.do_eval and
         p.activation in ('SWISH', 'RELU')):
       # Activation fused into the dropout kernel: one pass over the
-      # [*, hidden] tensor instead of two, each direction.
-      h = py_utils.DeterministicDropout(h, 1.0 - p.relu_dropout_prob,
-                                        act=p.activation)
+      # [*, hidden] tensor instead of two, each direction; its backward
+      # also yields db1.
+      h = py_utils.MatmulBiasDropout(x, theta.w1, theta.b1,
+                                     1.0 - p.relu_dropout_prob,
+                                     act=p.activation)
     else:
+      h = py_utils.MatmulBias(x, theta.w1, theta.b1)
       h = activations.GetFn(p.activation)(h)
       if p.relu_dropout_prob and not self.do_eval:
         h = py_utils.DeterministicDropout(h, 1.0 - p.relu_dropout_prob)
-    out = py_utils.MatmulBias(h, theta.w2, theta.b2)
     if p.residual_dropout_prob and not self.do_eval:
       # residual weight + padding mask fold into the dropout kernel.
-      return py_utils.DeterministicDropoutAdd(
-          out, 1.0 - p.residual_dropout_prob, inputs,
+      return py_utils.MatmulBiasDropoutAdd(
+          h, theta.w2, theta.b2, 1.0 - p.residual_dropout_prob, residual,
           scale=p.residual_weight, paddings=paddings)
+    out = py_utils.MatmulBias(h, theta.w2, theta.b2)
     if p.residual_weight != 1.0:
       out = out * p.residual_weight
     if paddings is not None:
       out = py_utils.ApplyPadding(paddings, out)
-    return inputs + out
+    return residual + out
 
 
 class MoETransformerFeedForwardLayer(BaseLayer):

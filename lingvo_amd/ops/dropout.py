@@ -77,6 +77,76 @@ class _DropoutFn(torch.autograd.Function):
     return dx, dres, None, None, None, None, None, None
 
 
+class _LinearDropoutFn(torch.autograd.Function):
+  """y = dropout(act(x @ w + b) * scale * (1 - pad)) (+ residual).
+
+  Forward is addmm + dropout_fwd, exactly the unfused pair. Backward
+  runs dropout_bwd_colsum, which writes dh and its fp32 column sums (db)
+  in one pass, then the two GEMMs autograd's addmm backward would issue.
+  Saves what the unfused pair saves: x, w, and h only when act != NONE.
+  """
+
+  @staticmethod
+  def forward(ctx, x2, w, b, residual, seed, keep, act, scale, pad):
+    ext = _loader.get_ext(required=True)
+    d = w.shape[1]
+    h = torch.addmm(b, x2, w)
+    y = ext.dropout_fwd(h, residual, seed, _StepSeedBuf(x2.device), keep,
+                        act, scale, pad, d)
+    ctx.seed, ctx.keep, ctx.act, ctx.scale, ctx.d = seed, keep, act, scale, d
+    ctx.has_res = residual is not None
+    ctx.has_pad = pad is not None
+    ctx.dev = x2.device
+    saved = [x2, w]
+    if act:
+      saved.append(h)
+    if pad is not None:
+      saved.append(pad)
+    ctx.save_for_backward(*saved)
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    ext = _loader.get_ext(required=True)
+    dy = dy.contiguous()
+    saved = list(ctx.saved_tensors)
+    x2, w = saved.pop(0), saved.pop(0)
+    h = saved.pop(0) if ctx.act else None
+    pad = saved.pop(0) if ctx.has_pad else None
+    dh, db = ext.dropout_bwd_colsum(dy, h, ctx.seed, _StepSeedBuf(ctx.dev),
+                                    ctx.keep, ctx.act, ctx.scale, pad, ctx.d)
+    dx = torch.mm(dh, w.t()) if ctx.needs_input_grad[0] else None
+    dw = torch.mm(x2.t(), dh) if ctx.needs_input_grad[1] else None
+    db = db.to(torch.bfloat16) if ctx.needs_input_grad[2] else None
+    dres = dy if ctx.has_res else None
+    return dx, dw, db, dres, None, None, None, None, None
+
+
+def linear_dropout(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor,
+                   keep_prob: float, seed: int,
+                   residual: Optional[torch.Tensor] = None,
+                   act: str = 'NONE', scale: float = 1.0,
+                   paddings: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """dropout(x @ w + b, ...) as in dropout(), as one autograd node whose
+  backward gets db from the dropout backward kernel. GPU bf16 only,
+  w.shape[1] % 8 == 0; paddings is [B, T] (or [rows]), 1.0 == padded."""
+  act_code = ACT_CODES[act.upper()]
+  assert not (act_code and residual is not None)
+  d = w.shape[1]
+  assert x.is_cuda and x.dtype == torch.bfloat16 and d % 8 == 0
+  x2 = x.reshape(-1, x.shape[-1])
+  pad = None
+  if paddings is not None:
+    pad = paddings.to(torch.bfloat16).contiguous()
+    assert pad.numel() == x2.shape[0]
+  res = None
+  if residual is not None:
+    res = residual.contiguous().reshape(-1, d)
+  y = _LinearDropoutFn.apply(x2, w, b, res, seed, keep_prob, act_code,
+                             scale, pad)
+  return y.reshape(*x.shape[:-1], d)
+
+
 def dropout(x: torch.Tensor, keep_prob: float, seed: int,
             residual: Optional[torch.Tensor] = None,
             act: str = 'NONE', scale: float = 1.0,

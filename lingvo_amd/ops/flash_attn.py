@@ -20,6 +20,7 @@ from typing import Optional, Tuple
 import torch
 
 from lingvo_amd.ops import _loader
+from lingvo_amd.ops import fusion
 
 
 def _ref_attention(q, k, v, klen, bias, win_l, win_r, bias_clip, scale,
@@ -103,6 +104,107 @@ class _FlashAttnFn(torch.autograd.Function):
             None, None, None)
 
 
+class _FlashAttnPackedFn(torch.autograd.Function):
+  """Self-attention on the packed projection output qkv [B,T,3*N*H]
+  (N == NKV). The kernels read q/k/v as strided views of qkv, and the
+  backward writes dq/dk/dv into the matching views of one dqkv buffer, so
+  neither the three input copies nor the split-backward cat exist."""
+
+  @staticmethod
+  def _views(t, n, h):
+    return [x.unflatten(-1, (n, h)) for x in t.split(n * h, dim=-1)]
+
+  @staticmethod
+  def forward(ctx, qkv, n, h, klen, bias, qseg, kseg, win_l, win_r,
+              bias_clip, scale, chunk_size, left_chunks):
+    ext = _loader.get_ext(required=True)
+    bias_b = None if bias is None else bias.to(torch.bfloat16).contiguous()
+    q, k, v = _FlashAttnPackedFn._views(qkv, n, h)
+    o, lse = ext.fa_fwd(q, k, v, klen, bias_b, qseg, kseg, win_l, win_r,
+                        bias_clip, scale, chunk_size, left_chunks)
+    empty = torch.empty(0)
+    ctx.save_for_backward(qkv, o, lse,
+                          klen if klen is not None else empty,
+                          bias_b if bias_b is not None else empty,
+                          qseg if qseg is not None else empty,
+                          kseg if kseg is not None else empty)
+    ctx.cfg = (n, h, win_l, win_r, bias_clip, scale, bias is not None and
+               bias.requires_grad, None if bias is None else bias.dtype,
+               chunk_size, left_chunks)
+    return o
+
+  @staticmethod
+  def backward(ctx, dout):
+    ext = _loader.get_ext(required=True)
+    qkv, o, lse, klen, bias_b, qseg, kseg = ctx.saved_tensors
+    (n, h, win_l, win_r, bias_clip, scale, bias_grad, bias_dtype,
+     chunk_size, left_chunks) = ctx.cfg
+    klen = klen if klen.numel() else None
+    bias_b = bias_b if bias_b.numel() else None
+    qseg = qseg if qseg.numel() else None
+    kseg = kseg if kseg.numel() else None
+    q, k, v = _FlashAttnPackedFn._views(qkv, n, h)
+    dqkv = torch.empty_like(qkv)
+    dq, dk, dv = _FlashAttnPackedFn._views(dqkv, n, h)
+    dbias = ext.fa_bwd(
+        dout.contiguous(), q, k, v, o, lse, klen, bias_b, qseg, kseg,
+        bias_grad, win_l, win_r, bias_clip, scale, chunk_size,
+        left_chunks, dq, dk, dv)[3]
+    dbias_out = dbias.to(bias_dtype) if bias_grad else None
+    return (dqkv, None, None, None, dbias_out, None, None, None, None,
+            None, None, None, None)
+
+
+def flash_attention_packed(qkv: torch.Tensor, num_heads: int,
+                           klen: Optional[torch.Tensor] = None,
+                           bias: Optional[torch.Tensor] = None,
+                           win_l: int = -1, win_r: int = -1,
+                           bias_clip: int = 127,
+                           scale: Optional[float] = None,
+                           q_segment_ids: Optional[torch.Tensor] = None,
+                           k_segment_ids: Optional[torch.Tensor] = None,
+                           chunk_size: int = 0, left_chunks: int = 0
+                           ) -> torch.Tensor:
+  """flash_attention on a packed self-attention projection: qkv is
+  [B,T,3*N*H] bf16 CUDA laid out [q | k | v] with N == NKV == num_heads.
+  Returns o [B,T,N,H]; the gradient is one [B,T,3*N*H] tensor."""
+  assert qkv.is_cuda and qkv.dtype == torch.bfloat16
+  assert qkv.shape[-1] % (3 * num_heads) == 0
+  h = qkv.shape[-1] // (3 * num_heads)
+  if scale is None:
+    scale = 1.0 / math.sqrt(h)
+  if klen is not None:
+    klen = klen.to(torch.int32).contiguous()
+  if q_segment_ids is not None:
+    q_segment_ids = q_segment_ids.to(torch.int32).contiguous()
+    k_segment_ids = k_segment_ids.to(torch.int32).contiguous()
+  return _FlashAttnPackedFn.apply(
+      qkv.contiguous(), num_heads, h, klen, bias, q_segment_ids,
+      k_segment_ids, win_l, win_r, bias_clip, scale, chunk_size,
+      left_chunks)
+
+
+def _meets_stride_contract(t: torch.Tensor) -> bool:
+  """The kernels' contract for q/k/v (flash_attn.hip check_strided_btnh):
+  dense [N][H], one uniform token-row stride that is a multiple of 8
+  elements, 16-byte aligned base."""
+  if t.dim() != 4 or t.dtype != torch.bfloat16:
+    return False
+  b, s, n, h = t.shape
+  if t.stride(3) != 1 or t.stride(2) != h:
+    return False
+  row = t.stride(1)
+  return (row % 8 == 0 and row >= n * h and t.stride(0) == s * row and
+          t.data_ptr() % 16 == 0)
+
+
+def _kernel_input(t: torch.Tensor) -> torch.Tensor:
+  t = t.to(torch.bfloat16)
+  if fusion.enabled() and _meets_stride_contract(t):
+    return t  # e.g. a split of a packed projection: no copy
+  return t.contiguous()
+
+
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     klen: Optional[torch.Tensor] = None,
                     bias: Optional[torch.Tensor] = None,
@@ -126,10 +228,9 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
   if q.is_cuda:
     orig = q.dtype
     out = _FlashAttnFn.apply(
-        q.to(torch.bfloat16).contiguous(), k.to(torch.bfloat16).contiguous(),
-        v.to(torch.bfloat16).contiguous(), klen, bias, q_segment_ids,
-        k_segment_ids, win_l, win_r, bias_clip, scale, chunk_size,
-        left_chunks)
+        _kernel_input(q), _kernel_input(k), _kernel_input(v), klen, bias,
+        q_segment_ids, k_segment_ids, win_l, win_r, bias_clip, scale,
+        chunk_size, left_chunks)
     return out.to(orig) if orig != torch.bfloat16 else out
   out = _ref_attention(q, k, v, klen, bias, win_l, win_r, bias_clip, scale,
                        q_segment_ids, k_segment_ids, chunk_size,

@@ -11,7 +11,8 @@ std::vector<torch::Tensor> layer_norm_fwd(torch::Tensor x,
 std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
                                           torch::Tensor scale,
                                           torch::Tensor mean,
-                                          torch::Tensor rstd, bool rms);
+                                          torch::Tensor rstd, bool rms,
+                                          c10::optional<torch::Tensor> dres);
 
 // mfma_probe.hip
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor bT);
@@ -37,7 +38,10 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
                                   bool bias_grad, int64_t win_l,
                                   int64_t win_r, int64_t bias_clip,
                                   double scale, int64_t chunk_size,
-                                  int64_t left_chunks);
+                                  int64_t left_chunks,
+                                  c10::optional<torch::Tensor> dq_out,
+                                  c10::optional<torch::Tensor> dk_out,
+                                  c10::optional<torch::Tensor> dv_out);
 
 // conv1d.hip
 torch::Tensor dwconv1d_fwd(torch::Tensor x, torch::Tensor w,
@@ -62,6 +66,10 @@ torch::Tensor dropout_bwd(torch::Tensor dy, c10::optional<torch::Tensor> x,
                           c10::optional<torch::Tensor> step_seed,
                           double keep, int64_t act, double scale,
                           c10::optional<torch::Tensor> pad, int64_t d);
+std::vector<torch::Tensor> dropout_bwd_colsum(
+    torch::Tensor dy, c10::optional<torch::Tensor> x, int64_t seed,
+    c10::optional<torch::Tensor> step_seed, double keep, int64_t act,
+    double scale, c10::optional<torch::Tensor> pad, int64_t d);
 
 // group_norm.hip
 std::vector<torch::Tensor> group_norm_fwd(torch::Tensor x,
@@ -166,16 +174,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_gates_bwd", &lstm_gates_bwd_op, "Fused LSTM gates bwd");
   m.def("dropout_fwd", &dropout_fwd, "Fused dropout fwd");
   m.def("dropout_bwd", &dropout_bwd, "Fused dropout bwd");
+  m.def("dropout_bwd_colsum", &dropout_bwd_colsum,
+        "Fused dropout bwd + fp32 column sums of dx");
   m.def("xent_fwd", &xent_fwd, "Fused softmax-xent fwd");
   m.def("xent_bwd", &xent_bwd, "Fused softmax-xent bwd");
   m.def("dwconv1d_fwd", &dwconv1d_fwd, "Depthwise time conv fwd");
   m.def("dwconv1d_bwd", &dwconv1d_bwd, "Depthwise time conv bwd");
   m.def("layer_norm_fwd", &layer_norm_fwd, "Fused LayerNorm/RMSNorm fwd");
-  m.def("layer_norm_bwd", &layer_norm_bwd, "Fused LayerNorm/RMSNorm bwd");
+  m.def("layer_norm_bwd", &layer_norm_bwd, "Fused LayerNorm/RMSNorm bwd",
+        py::arg("dy"), py::arg("x"), py::arg("scale"), py::arg("mean"),
+        py::arg("rstd"), py::arg("rms"), py::arg("dres") = py::none());
   m.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 layout probe");
   m.def("fa_fwd", &fa_fwd, "Flash attention forward");
-  m.def("fa_bwd", &fa_bwd, "Flash attention backward");
+  m.def("fa_bwd", &fa_bwd, "Flash attention backward", py::arg("dout"),
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+        py::arg("lse"), py::arg("klen"), py::arg("bias"), py::arg("qseg"),
+        py::arg("kseg"), py::arg("bias_grad"), py::arg("win_l"),
+        py::arg("win_r"), py::arg("bias_clip"), py::arg("scale"),
+        py::arg("chunk_size"), py::arg("left_chunks"),
+        py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
+        py::arg("dv_out") = py::none());
   m.def("emb_gather", &emb_gather, "Embedding gather fwd");
   m.def("emb_scatter_add", &emb_scatter_add,
         "Deterministic embedding scatter-add bwd");

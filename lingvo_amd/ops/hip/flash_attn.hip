@@ -143,7 +143,10 @@ __global__ __launch_bounds__(FWD_BLOCK) void fa_fwd_kernel(
     const int* __restrict__ kseg,              // [B][S] or null
     unsigned short* __restrict__ o, float* __restrict__ lse, int B, int T,
     int S, int N, int NKV, int win_l, int win_r, int bias_clip, float scale,
-    int chunk, int lc) {
+    int chunk, int lc,
+    // Token-row strides of q/k/v in elements ([n][h] stays dense): N*H for
+    // a contiguous tensor, the packed width for views of a QKV projection.
+    long sq, long sk, long sv) {
   constexpr int ROWB = H * 2;
   constexpr int KH = H / 32;   // mfma K-steps over head dim
   constexpr int HF = H / 16;   // output col frags
@@ -173,7 +176,7 @@ __global__ __launch_bounds__(FWD_BLOCK) void fa_fwd_kernel(
     int qrow = q0 + cl;
     if (qrow < T) {
       qfrag[kk] = load_bf16x8_bits(
-          q + (((long)b * T + qrow) * N + n) * H + kk * 32 + g * 8);
+          q + ((long)b * T + qrow) * sq + n * H + kk * 32 + g * 8);
     } else {
       float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       qfrag[kk] = pack_bf16x8(z);
@@ -238,11 +241,9 @@ __global__ __launch_bounds__(FWD_BLOCK) void fa_fwd_kernel(
     const int kbase = kt * KTF;
     // Stage K and V^T.
     stage_regular<H, KTF, FWD_BLOCK>(
-        k + (((long)b * S + kbase) * NKV + nkv) * H, (long)NKV * H,
-        klen - kbase, k_lds);
+        k + ((long)b * S + kbase) * sk + nkv * H, sk, klen - kbase, k_lds);
     stage_transposed<H, KTF, FWD_BLOCK>(
-        v + (((long)b * S + kbase) * NKV + nkv) * H, (long)NKV * H,
-        klen - kbase, vt_lds);
+        v + ((long)b * S + kbase) * sv + nkv * H, sv, klen - kbase, vt_lds);
     __syncthreads();
 
     // S strip: 16 q rows x KTF keys, fp32.
@@ -412,7 +413,9 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
     unsigned short* __restrict__ dk, unsigned short* __restrict__ dv,
     float* __restrict__ dbias, int B, int T, int S, int N, int NKV,
     int win_l, int win_r, int bias_clip, float scale, int skip,
-    int chunk, int lc) {
+    int chunk, int lc,
+    // Token-row strides in elements of q/k/v (reads) and dk/dv (writes).
+    long sq, long sk, long sv, long sdk, long sdv) {
   constexpr int ROWB = H * 2;
   constexpr int KH = H / 32;
   constexpr int HF = H / 16;
@@ -446,8 +449,7 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
 
   // Stage K^T once (shared by all heads in the group).
   stage_transposed<H, KTB, NWB * WAVE_SIZE>(
-      k + (((long)b * S + kbase) * NKV + nkv) * H, (long)NKV * H,
-      klen - kbase, kt_lds);
+      k + ((long)b * S + kbase) * sk + nkv * H, sk, klen - kbase, kt_lds);
 
   // K, V fragments (A layout) from global: row = key (cl), k = h.
   bf16x8 kfrag[KH], vfrag[KH];
@@ -457,9 +459,10 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
 #pragma unroll
     for (int kk = 0; kk < KH; ++kk) {
       if (ok) {
-        long off = (((long)b * S + key) * NKV + nkv) * H + kk * 32 + g * 8;
-        kfrag[kk] = load_bf16x8_bits(k + off);
-        vfrag[kk] = load_bf16x8_bits(v + off);
+        const long tok = (long)b * S + key;
+        const int col = nkv * H + kk * 32 + g * 8;
+        kfrag[kk] = load_bf16x8_bits(k + tok * sk + col);
+        vfrag[kk] = load_bf16x8_bits(v + tok * sv + col);
       } else {
         float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         kfrag[kk] = pack_bf16x8(z);
@@ -484,11 +487,11 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
         for (int r = 0; r < 4; ++r) {
           const int key = k0 + g * 4 + r;
           if (key >= S) continue;
-          long off = (((long)b * S + key) * NKV + nkv) * H;
+          const long tok = (long)b * S + key;
 #pragma unroll
           for (int hf = 0; hf < HF; ++hf) {
-            dk[off + hf * 16 + cl] = float_to_bf16_bits(0.f);
-            dv[off + hf * 16 + cl] = float_to_bf16_bits(0.f);
+            dk[tok * sdk + nkv * H + hf * 16 + cl] = float_to_bf16_bits(0.f);
+            dv[tok * sdv + nkv * H + hf * 16 + cl] = float_to_bf16_bits(0.f);
           }
         }
       }
@@ -515,15 +518,13 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
       const int qb = qt2 * QTB;
       __syncthreads();
       stage_regular<H, QTB, NWB * WAVE_SIZE>(
-          q + (((long)b * T + qb) * N + n) * H, (long)N * H, T - qb,
-          q_lds);
+          q + ((long)b * T + qb) * sq + n * H, sq, T - qb, q_lds);
       stage_regular<H, QTB, NWB * WAVE_SIZE>(
           dout + (((long)b * T + qb) * N + n) * H, (long)N * H, T - qb,
           do_lds);
       if (!(skip & 2)) {
         stage_transposed<H, QTB, NWB * WAVE_SIZE, TP>(
-            q + (((long)b * T + qb) * N + n) * H, (long)N * H, T - qb,
-            qt_lds);
+            q + ((long)b * T + qb) * sq + n * H, sq, T - qb, qt_lds);
         stage_transposed<H, QTB, NWB * WAVE_SIZE, TP>(
             dout + (((long)b * T + qb) * N + n) * H, (long)N * H, T - qb,
             dot_lds);
@@ -745,12 +746,16 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
     for (int r = 0; r < 4; ++r) {
       const int key = k0 + g * 4 + r;
       if (key >= S) continue;  // acc is 0 for klen<=key<S: writes zeros
-      long off = (((long)b * S + key) * NKV + nkv) * H;
+      const long tok = (long)b * S + key;
+      // fp32 GQA buffers are always dense.
+      const long off = (tok * NKV + nkv) * H;
 #pragma unroll
       for (int hf = 0; hf < HF; ++hf) {
         if (group == 1) {
-          dk[off + hf * 16 + cl] = float_to_bf16_bits(acc_dk[hf][r]);
-          dv[off + hf * 16 + cl] = float_to_bf16_bits(acc_dv[hf][r]);
+          dk[tok * sdk + nkv * H + hf * 16 + cl] =
+              float_to_bf16_bits(acc_dk[hf][r]);
+          dv[tok * sdv + nkv * H + hf * 16 + cl] =
+              float_to_bf16_bits(acc_dv[hf][r]);
         } else {
           // GQA: multiple heads accumulate; use fp32 atomics into dq_acc?
           // dk/dv are bf16 outputs; for group>1 the host passes fp32
@@ -767,6 +772,28 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
   }
 }
 
+// dq_acc fp32 dense [rows, NH] -> bf16 dq with token-row stride sdq: the
+// `.to(bf16)` cast of the dense path, written into a view of a packed
+// dQKV buffer. One 8-wide vector per thread; grid.y walks rows.
+__global__ void fa_dq_cast(const float* __restrict__ dq_acc,
+                           unsigned short* __restrict__ dq, long rows,
+                           int nh_vec, long sdq) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nh_vec) return;
+  for (long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const float* src = dq_acc + (r * nh_vec + c) * 8;
+    floatx4 a = *reinterpret_cast<const floatx4*>(src);
+    floatx4 b = *reinterpret_cast<const floatx4*>(src + 4);
+    ushortx8 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      o[j] = float_to_bf16_bits(a[j]);
+      o[4 + j] = float_to_bf16_bits(b[j]);
+    }
+    *reinterpret_cast<ushortx8*>(dq + r * sdq + (long)c * 8) = o;
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -778,6 +805,31 @@ static void check_btnh(const torch::Tensor& t, const char* name) {
               name, " must be contiguous bf16 [B,T,N,H]");
 }
 
+// Stride contract for q/k/v and caller-provided dq/dk/dv: bf16 [B,T,N,H]
+// whose [N][H] dims are dense, whose token rows (b, t) sit at one uniform
+// stride that is a multiple of 8 elements and at least N*H, and whose base
+// is 16-byte aligned (every access is an aligned 16-byte vector or lies
+// inside one). Returns the row stride in elements.
+static long check_strided_btnh(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 &&
+                  t.scalar_type() == torch::kBFloat16,
+              name, " must be a CUDA bf16 [B,T,N,H] tensor");
+  const long N = t.size(2), H = t.size(3);
+  TORCH_CHECK((H == 1 || t.stride(3) == 1) && (N == 1 || t.stride(2) == H),
+              name, ": the [N][H] dims must be dense");
+  const long row = t.size(1) == 1 && t.size(0) == 1 ? N * H : (
+      t.size(1) == 1 ? t.stride(0) : t.stride(1));
+  TORCH_CHECK(t.size(0) == 1 || t.size(1) == 1 ||
+                  t.stride(0) == t.size(1) * row,
+              name, ": batch stride must be T * row stride");
+  TORCH_CHECK(row % 8 == 0 && row >= N * H, name,
+              ": row stride must be a multiple of 8 elements and >= N*H, got ",
+              row);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              ": base pointer must be 16-byte aligned");
+  return row;
+}
+
 std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
                                   torch::Tensor v,
                                   c10::optional<torch::Tensor> klen,
@@ -787,14 +839,16 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
                                   int64_t win_l, int64_t win_r,
                                   int64_t bias_clip, double scale,
                                   int64_t chunk_size, int64_t left_chunks) {
-  check_btnh(q, "q");
-  check_btnh(k, "k");
-  check_btnh(v, "v");
+  const long sq = check_strided_btnh(q, "q");
+  const long sk = check_strided_btnh(k, "k");
+  const long sv = check_strided_btnh(v, "v");
   const int B = q.size(0), T = q.size(1), N = q.size(2), H = q.size(3);
   const int S = k.size(1), NKV = k.size(2);
   TORCH_CHECK(H == 64 || H == 128, "H must be 64 or 128, got ", H);
   TORCH_CHECK(N % NKV == 0, "GQA requires N % NKV == 0");
-  auto o = torch::empty_like(q);
+  TORCH_CHECK(k.size(0) == B && k.size(3) == H && v.sizes() == k.sizes(),
+              "k/v must be [B,S,NKV,H]");
+  auto o = torch::empty({B, T, N, H}, q.options());
   auto lse = torch::empty({B, N, T}, q.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
   dim3 grid((T + FQT - 1) / FQT, N, B);
@@ -818,7 +872,7 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
                      (const unsigned short*)v.data_ptr(), klp, bp, qsp,     \
                      ksp, (unsigned short*)o.data_ptr(),                    \
                      lse.data_ptr<float>(), B, T, S, N, NKV, (int)win_l,    \
-                     (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks)
+                     (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv)
 #define FA_FWD64(HH)                                                        \
   hipLaunchKernelGGL((fa_fwd_kernel<HH, 64, false>), grid,                  \
                      dim3(FWD_BLOCK),                                       \
@@ -827,7 +881,7 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
                      (const unsigned short*)v.data_ptr(), klp, bp, qsp,     \
                      ksp, (unsigned short*)o.data_ptr(),                    \
                      lse.data_ptr<float>(), B, T, S, N, NKV, (int)win_l,    \
-                     (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks)
+                     (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv)
 #define FA_FWD_SEG(HH)                                                      \
   if (ktf == 128)                                                           \
     hipLaunchKernelGGL((fa_fwd_kernel<HH, 128, true>), grid,                \
@@ -837,7 +891,7 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
                        (const unsigned short*)v.data_ptr(), klp, bp, qsp,   \
                        ksp, (unsigned short*)o.data_ptr(),                  \
                        lse.data_ptr<float>(), B, T, S, N, NKV, (int)win_l,  \
-                       (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks);           \
+                       (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv);           \
   else                                                                      \
     hipLaunchKernelGGL((fa_fwd_kernel<HH, 64, true>), grid,                 \
                        dim3(FWD_BLOCK), shmem, stream,                      \
@@ -846,7 +900,7 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
                        (const unsigned short*)v.data_ptr(), klp, bp, qsp,   \
                        ksp, (unsigned short*)o.data_ptr(),                  \
                        lse.data_ptr<float>(), B, T, S, N, NKV, (int)win_l,  \
-                       (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks)
+                       (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv)
   if (qsp != nullptr) {
     if (H == 64) {
       FA_FWD_SEG(64);
@@ -876,11 +930,43 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
                                   bool bias_grad, int64_t win_l,
                                   int64_t win_r, int64_t bias_clip,
                                   double scale, int64_t chunk_size,
-                                  int64_t left_chunks) {
-  check_btnh(q, "q");
+                                  int64_t left_chunks,
+                                  c10::optional<torch::Tensor> dq_out,
+                                  c10::optional<torch::Tensor> dk_out,
+                                  c10::optional<torch::Tensor> dv_out) {
+  // Every check comes before the first allocation or launch, so a
+  // rejected call leaves caller-provided outputs untouched.
+  const long sq = check_strided_btnh(q, "q");
+  const long sk = check_strided_btnh(k, "k");
+  const long sv = check_strided_btnh(v, "v");
+  check_btnh(dout, "dout");
+  check_btnh(o, "o");
   const int B = q.size(0), T = q.size(1), N = q.size(2), H = q.size(3);
   const int S = k.size(1), NKV = k.size(2);
+  TORCH_CHECK(H == 64 || H == 128, "H must be 64 or 128, got ", H);
+  TORCH_CHECK(N % NKV == 0, "GQA requires N % NKV == 0");
+  TORCH_CHECK(k.size(0) == B && k.size(3) == H && v.sizes() == k.sizes(),
+              "k/v must be [B,S,NKV,H]");
+  TORCH_CHECK(dout.size(0) == B && dout.size(1) == T && dout.size(2) == N &&
+                  dout.size(3) == H && o.sizes() == dout.sizes(),
+              "dout/o must be [B,T,N,H]");
   const int group = N / NKV;
+  // Caller-provided outputs: dk/dv are written by the main kernel and dq by
+  // the cast kernel, straight into (views of) the caller's buffers.
+  const bool into = dq_out.has_value();
+  TORCH_CHECK(dk_out.has_value() == into && dv_out.has_value() == into,
+              "dq_out, dk_out and dv_out come together");
+  long sdq = (long)N * H, sdk = (long)NKV * H, sdv = (long)NKV * H;
+  if (into) {
+    TORCH_CHECK(group == 1, "caller-provided outputs need N == NKV");
+    sdq = check_strided_btnh(*dq_out, "dq_out");
+    sdk = check_strided_btnh(*dk_out, "dk_out");
+    sdv = check_strided_btnh(*dv_out, "dv_out");
+    TORCH_CHECK(dq_out->sizes() == dout.sizes() &&
+                    dk_out->sizes() == k.sizes() &&
+                    dv_out->sizes() == k.sizes(),
+                "dq_out/dk_out/dv_out must have the shapes of q/k/v");
+  }
   auto stream = at::cuda::getCurrentCUDAStream();
 
   auto delta = torch::empty({B, N, T}, q.options().dtype(torch::kFloat32));
@@ -899,14 +985,18 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
                          delta.data_ptr<float>(), B, T, N);
   }
 
-  auto dq_acc = torch::zeros_like(q, q.options().dtype(torch::kFloat32));
+  auto fopts = q.options().dtype(torch::kFloat32);
+  auto dq_acc = torch::zeros({B, T, N, H}, fopts);
   torch::Tensor dk_t, dv_t;
-  if (group == 1) {
-    dk_t = torch::empty_like(k);
-    dv_t = torch::empty_like(v);
+  if (into) {
+    dk_t = *dk_out;
+    dv_t = *dv_out;
+  } else if (group == 1) {
+    dk_t = torch::empty({B, S, NKV, H}, q.options());
+    dv_t = torch::empty({B, S, NKV, H}, q.options());
   } else {
-    dk_t = torch::zeros_like(k, k.options().dtype(torch::kFloat32));
-    dv_t = torch::zeros_like(v, v.options().dtype(torch::kFloat32));
+    dk_t = torch::zeros({B, S, NKV, H}, fopts);
+    dv_t = torch::zeros({B, S, NKV, H}, fopts);
   }
   const int nbias = 2 * (int)bias_clip + 1;
   torch::Tensor dbias_t = torch::zeros(
@@ -954,7 +1044,7 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
       dq_acc.data_ptr<float>(),                                              \
       (unsigned short*)dk_t.data_ptr(), (unsigned short*)dv_t.data_ptr(),    \
       dbias_t.numel() ? dbias_t.data_ptr<float>() : nullptr, B, T, S, N,     \
-      NKV, (int)win_l, (int)win_r, (int)bias_clip, (float)scale, skip_phases, (int)chunk_size, (int)left_chunks)
+      NKV, (int)win_l, (int)win_r, (int)bias_clip, (float)scale, skip_phases, (int)chunk_size, (int)left_chunks, sq, sk, sv, sdk, sdv)
   if (H == 64) {
     if (bg) FA_BWD(64, true); else FA_BWD(64, false);
   } else {
@@ -962,7 +1052,18 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
   }
 #undef FA_BWD
 
-  auto dq = dq_acc.to(torch::kBFloat16);
+  torch::Tensor dq;
+  if (into) {
+    dq = *dq_out;
+    const long rows = (long)B * T;
+    const int nh_vec = N * H / 8;
+    dim3 cgrid(cdiv(nh_vec, 256), (unsigned)std::min<long>(rows, 4096));
+    hipLaunchKernelGGL(fa_dq_cast, cgrid, dim3(256), 0, stream,
+                       dq_acc.data_ptr<float>(), (unsigned short*)dq.data_ptr(),
+                       rows, nh_vec, sdq);
+  } else {
+    dq = dq_acc.to(torch::kBFloat16);
+  }
   auto dk = group == 1 ? dk_t : dk_t.to(torch::kBFloat16);
   auto dv = group == 1 ? dv_t : dv_t.to(torch::kBFloat16);
   return {dq, dk, dv, dbias_t};

@@ -89,6 +89,9 @@ __global__ void ln_fwd_bf16(const unsigned short* __restrict__ x,
 // ---- backward ------------------------------------------------------------
 // dx in one pass; per-wave column partials for dscale/dbias written to
 // partials [2, nwaves, D] (dscale at slab 0, dbias at slab 1).
+// dres (optional, x's shape): the gradient of a residual branch that forks
+// off x; stored dx = bf16(dx_fp32 + dres), one rounding instead of the two
+// of a separate add kernel. It does not enter dscale/dbias.
 template <int NVEC, bool RMS>
 __global__ void ln_bwd_bf16(const unsigned short* __restrict__ dy,
                             const unsigned short* __restrict__ x,
@@ -96,7 +99,8 @@ __global__ void ln_bwd_bf16(const unsigned short* __restrict__ dy,
                             const float* __restrict__ mean,
                             const float* __restrict__ rstd,
                             unsigned short* __restrict__ dx,
-                            float* __restrict__ partials, int rows, int D) {
+                            float* __restrict__ partials, int rows, int D,
+                            const unsigned short* __restrict__ dres) {
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = (blockIdx.x * kWavesPerBlock) + (threadIdx.x / WAVE_SIZE);
   const int nwaves = gridDim.x * kWavesPerBlock;
@@ -123,11 +127,15 @@ __global__ void ln_bwd_bf16(const unsigned short* __restrict__ dy,
     float mu = RMS ? 0.f : mean[row];
     float rs = rstd[row];
     float xhat[NVEC], g[NVEC];
+    ushortx8 rv[NVEC / 8];
     float s1 = 0.f, s2 = 0.f;  // sum(dxhat), sum(dxhat*xhat)
 #pragma unroll
     for (int v = 0; v < NVEC; v += 8) {
       ushortx8 xv = *reinterpret_cast<const ushortx8*>(xr + v);
       ushortx8 dv = *reinterpret_cast<const ushortx8*>(dyr + v);
+      if (dres)
+        rv[v / 8] = *reinterpret_cast<const ushortx8*>(
+            dres + (long)row * D + lane * NVEC + v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float xh = (bf16_bits_to_float(xv[j]) - mu) * rs;
@@ -151,6 +159,7 @@ __global__ void ln_bwd_bf16(const unsigned short* __restrict__ dy,
       for (int j = 0; j < 8; ++j) {
         float val = RMS ? rs * (g[v + j] - xhat[v + j] * s2)
                         : rs * (g[v + j] - s1 - xhat[v + j] * s2);
+        if (dres) val += bf16_bits_to_float(rv[v / 8][j]);
         ov[j] = float_to_bf16_bits(val);
       }
       *reinterpret_cast<ushortx8*>(dxr + v) = ov;
@@ -261,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void ln_bwd_big(
     const unsigned short* __restrict__ scale,
     const float* __restrict__ mean, const float* __restrict__ rstd,
     unsigned short* __restrict__ dx, float* __restrict__ partials,
-    int rows, int D) {
+    int rows, int D, const unsigned short* __restrict__ dres) {
   __shared__ float scratch[kWavesPerBlock];
   const int tid = threadIdx.x;
   float ds_acc[ITERS][8];
@@ -310,6 +319,9 @@ __global__ __launch_bounds__(kBlock) void ln_bwd_big(
         ushortx8 xv = *reinterpret_cast<const ushortx8*>(xr + base);
         ushortx8 dv = *reinterpret_cast<const ushortx8*>(dyr + base);
         ushortx8 ws = *reinterpret_cast<const ushortx8*>(scale + base);
+        ushortx8 rv;
+        if (dres)
+          rv = *reinterpret_cast<const ushortx8*>(dres + (long)row * D + base);
         ushortx8 ov;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -318,6 +330,7 @@ __global__ __launch_bounds__(kBlock) void ln_bwd_big(
                         (1.f + bf16_bits_to_float(ws[j]));
           float val = RMS ? rs * (dxhat - xh * s2)
                           : rs * (dxhat - s1 - xh * s2);
+          if (dres) val += bf16_bits_to_float(rv[j]);
           ov[j] = float_to_bf16_bits(val);
         }
         *reinterpret_cast<ushortx8*>(dxr + base) = ov;
@@ -386,7 +399,8 @@ __global__ void ln_bwd_generic(const unsigned short* __restrict__ dy,
                                const float* __restrict__ rstd,
                                unsigned short* __restrict__ dx,
                                float* __restrict__ partials, int rows,
-                               int D) {
+                               int D,
+                               const unsigned short* __restrict__ dres) {
   __shared__ float scratch[kWavesPerBlock];
   float* ds = partials + (long)blockIdx.x * D;
   float* db = partials + (long)(gridDim.x + blockIdx.x) * D;
@@ -420,6 +434,7 @@ __global__ void ln_bwd_generic(const unsigned short* __restrict__ dy,
       float w = 1.f + bf16_bits_to_float(scale[i]);
       float dxhat = dyr ? bf16_bits_to_float(dyr[i]) * w : 0.f;
       float val = RMS ? rs * (dxhat - xh * s2) : rs * (dxhat - s1 - xh * s2);
+      if (dres) val += bf16_bits_to_float(dres[(long)row * D + i]);
       dxr[i] = float_to_bf16_bits(val);
     }
     __syncthreads();
@@ -524,9 +539,15 @@ std::vector<torch::Tensor> layer_norm_fwd(torch::Tensor x, torch::Tensor scale,
 std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
                                           torch::Tensor scale,
                                           torch::Tensor mean,
-                                          torch::Tensor rstd, bool rms) {
+                                          torch::Tensor rstd, bool rms,
+                                          c10::optional<torch::Tensor> dres) {
   const long D = x.size(-1);
   const long rows = x.numel() / D;
+  TORCH_CHECK(!dres.has_value() ||
+              (dres->is_cuda() && dres->is_contiguous() &&
+               dres->scalar_type() == torch::kBFloat16 &&
+               dres->numel() == x.numel()),
+              "dres must be contiguous CUDA bf16 of x's shape");
   auto dx = torch::empty_like(x);
   auto opts = x.options().dtype(torch::kFloat32);
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -537,6 +558,8 @@ std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
   const float* mp = rms ? nullptr : mean.data_ptr<float>();
   const float* rp = rstd.data_ptr<float>();
   unsigned short* dxp = (unsigned short*)dx.data_ptr();
+  const unsigned short* drp =
+      dres.has_value() ? (const unsigned short*)dres->data_ptr() : nullptr;
 
   torch::Tensor dscale = torch::zeros({D}, opts);
   torch::Tensor dbias = torch::zeros({D}, opts);
@@ -552,12 +575,12 @@ std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
       hipLaunchKernelGGL((ln_bwd_bf16<NV, true>), dim3(grid),            \
                          dim3(kBlock), 0, stream, dyp, xp, sp, mp, rp,   \
                          dxp, partials.data_ptr<float>(), (int)rows,     \
-                         (int)D);                                        \
+                         (int)D, drp);                                   \
     else                                                                 \
       hipLaunchKernelGGL((ln_bwd_bf16<NV, false>), dim3(grid),           \
                          dim3(kBlock), 0, stream, dyp, xp, sp, mp, rp,   \
                          dxp, partials.data_ptr<float>(), (int)rows,     \
-                         (int)D);                                        \
+                         (int)D, drp);                                   \
     break;
     switch (nvec) {
       LN_BWD_CASE(8)
@@ -583,12 +606,12 @@ std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
       hipLaunchKernelGGL((ln_bwd_big<true, IT>), dim3(grid),              \
                          dim3(kBlock), 0, stream, dyp, xp, sp, mp, rp,    \
                          dxp, partials.data_ptr<float>(), (int)rows,      \
-                         (int)D);                                         \
+                         (int)D, drp);                                    \
     else                                                                  \
       hipLaunchKernelGGL((ln_bwd_big<false, IT>), dim3(grid),             \
                          dim3(kBlock), 0, stream, dyp, xp, sp, mp, rp,    \
                          dxp, partials.data_ptr<float>(), (int)rows,      \
-                         (int)D);                                         \
+                         (int)D, drp);                                    \
     break;
     switch (big_iters(D)) {
       LN_BWD_BIG(1)
@@ -608,11 +631,11 @@ std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
     if (rms)
       hipLaunchKernelGGL((ln_bwd_generic<true>), dim3(grid), dim3(kBlock), 0,
                          stream, dyp, xp, sp, mp, rp, dxp,
-                         partials.data_ptr<float>(), (int)rows, (int)D);
+                         partials.data_ptr<float>(), (int)rows, (int)D, drp);
     else
       hipLaunchKernelGGL((ln_bwd_generic<false>), dim3(grid), dim3(kBlock), 0,
                          stream, dyp, xp, sp, mp, rp, dxp,
-                         partials.data_ptr<float>(), (int)rows, (int)D);
+                         partials.data_ptr<float>(), (int)rows, (int)D, drp);
     int splitk2 = (int)std::min<long>(64, std::max<long>(1, grid / 8));
     hipLaunchKernelGGL(ln_bwd_reduce, dim3(cdiv(D, 256), splitk2), dim3(256),
                        0, stream, partials.data_ptr<float>(),

@@ -37,6 +37,41 @@ class _LayerNormFn(torch.autograd.Function):
     return dx, dscale, dbias, None, None
 
 
+class _LayerNormResFn(torch.autograd.Function):
+  """(LN(x), x): the second output is x itself, handed to the residual
+  branch of a pre-LN block so that both gradients of the fork arrive
+  here and the residual one is added inside the LN backward kernel
+  instead of by a separate autograd add over [rows, D]."""
+
+  @staticmethod
+  def forward(ctx, x, scale, bias, eps, rms):
+    ctx.set_materialize_grads(False)
+    return _LayerNormFn.forward(ctx, x, scale, bias, eps, rms), x
+
+  @staticmethod
+  def backward(ctx, dy, dres):
+    if dy is None:
+      return dres, None, None, None, None
+    if dres is None:
+      return _LayerNormFn.backward(ctx, dy)
+    ext = _loader.get_ext(required=True)
+    x, scale_b, mean, rstd = ctx.saved_tensors
+    dx, dscale, dbias = ext.layer_norm_bwd(
+        dy.contiguous().to(torch.bfloat16), x, scale_b, mean, rstd, ctx.rms,
+        dres.contiguous().to(torch.bfloat16))
+    dscale = dscale.to(ctx.scale_dtype)
+    dbias = None if ctx.rms else dbias.to(ctx.scale_dtype)
+    return dx, dscale, dbias, None, None
+
+
+def layer_norm_with_residual(x: torch.Tensor, scale: torch.Tensor,
+                             bias: torch.Tensor, eps: float = 1e-6):
+  """Returns (layer_norm(x), x) for bf16 CUDA x; feed the second value
+  to the block's residual add (see _LayerNormResFn)."""
+  assert x.is_cuda and x.dtype == torch.bfloat16
+  return _LayerNormResFn.apply(x, scale, bias, eps, False)
+
+
 def layer_norm(x: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor,
                eps: float = 1e-6) -> torch.Tensor:
   """y = (x - mean)/sqrt(var+eps) * (1+scale) + bias over the last dim."""
