@@ -524,6 +524,179 @@ class CtcDecoder(BaseLayer):
         'use GreedyDecode (decode_num_hyps=1)')
 
 
+class TransducerDecoder(BaseLayer):
+  """Transducer (RNN-T) decoder: an LSTM prediction network over the label
+  history, a joint network tanh(W_e enc_t + W_p pred_u) -> vocabulary over
+  every (frame, label position) pair, trained with the transducer loss
+  (ops.rnnt) and decoded time-synchronously. Has the four methods AsrModel
+  and StreamingRecognizer reach a decoder through, with AsrDecoder's
+  signatures."""
+
+  @classmethod
+  def Params(cls):
+    p = super().Params()
+    p.Define('vocab_size', 1024, 'Output vocab, blank included.')
+    p.Define('emb_dim', 128, 'Token embedding dim.')
+    p.Define('rnn_cell_dim', 640, 'Prediction network LSTM dim.')
+    p.Define('num_lstm_layers', 1, 'Prediction network LSTM layers.')
+    p.Define('source_dim', 512, 'Encoder output dim.')
+    p.Define('joint_dim', 640, 'Joint network dim.')
+    p.Define('blank_id', 0, 'Id of the blank; also starts the history.')
+    p.Define('dropout_prob', 0.1,
+             'Dropout on the encoder and prediction network outputs.')
+    p.Define('max_symbols_per_frame', 3,
+             'GreedyDecode emits at most this many labels per frame.')
+    p.Define('rnnt_impl', 'auto',
+             "ops.rnnt.rnnt_loss impl: 'auto' (HIP kernels on GPU, torch "
+             "twin on CPU) or 'torch' (fp32 log_softmax + torch ops).")
+    return p
+
+  def __init__(self, params):
+    super().__init__(params)
+    p = self.p
+    assert 0 <= p.blank_id < p.vocab_size
+    assert p.num_lstm_layers >= 1 and p.max_symbols_per_frame >= 1
+    self.CreateChild('emb', lingvo_layers.EmbeddingLayer.Params().Set(
+        vocab_size=p.vocab_size, embedding_dim=p.emb_dim))
+    cells = []
+    for i in range(p.num_lstm_layers):
+      cells.append(rnn_cell.LSTMCellSimple.Params().Set(
+          name=f'lstm_{i}',
+          num_input_nodes=p.emb_dim if i == 0 else p.rnn_cell_dim,
+          num_output_nodes=p.rnn_cell_dim))
+    self.CreateChildren('rnns', cells)
+    self.CreateChild('enc_proj', lingvo_layers.ProjectionLayer.Params().Set(
+        input_dim=p.source_dim, output_dim=p.joint_dim, has_bias=True))
+    self.CreateChild('pred_proj', lingvo_layers.ProjectionLayer.Params().Set(
+        input_dim=p.rnn_cell_dim, output_dim=p.joint_dim))
+    self.CreateChild('softmax', lingvo_layers.SimpleFullSoftmax.Params().Set(
+        input_dim=p.joint_dim, num_classes=p.vocab_size))
+
+  def _InitStates(self, batch: int, device):
+    return [c.InitState(batch, device, self.fprop_dtype) for c in self.rnns]
+
+  def _PredictionStep(self, theta: NestedMap, tok: torch.Tensor, states):
+    """One step of the prediction network: ids [B] -> (projected output
+    [B, joint_dim], new states)."""
+    x = self.emb.EmbLookup(theta.emb, tok).to(self.fprop_dtype)
+    new_states = []
+    for i, cell in enumerate(self.rnns):
+      st = cell.FProp(theta.rnns[i], states[i], NestedMap(act=x))
+      new_states.append(st)
+      x = st.m
+    return x, new_states
+
+  def _Joint(self, theta: NestedMap, enc_p: torch.Tensor,
+             pred_p: torch.Tensor) -> torch.Tensor:
+    """enc_p [..., joint_dim] + pred_p [..., joint_dim] (broadcast by the
+    caller) -> logits [..., V]."""
+    return self.softmax.Logits(theta.softmax, torch.tanh(enc_p + pred_p))
+
+  def ComputePredictions(self, theta: NestedMap, enc: torch.Tensor,
+                         enc_paddings: torch.Tensor,
+                         targets: NestedMap) -> NestedMap:
+    p = self.p
+    ids = targets.ids.long()
+    b = ids.shape[0]
+    # History [blank, y_1 .. y_U]: U+1 prediction network outputs.
+    hist = torch.cat([torch.full_like(ids[:, :1], p.blank_id), ids], dim=1)
+    states = self._InitStates(b, enc.device)
+    outs = []
+    for u in range(hist.shape[1]):
+      out, states = self._PredictionStep(theta, hist[:, u], states)
+      outs.append(out)
+    pred = torch.stack(outs, dim=1)                         # [B, U+1, H]
+    enc = enc.to(self.fprop_dtype)
+    if p.dropout_prob and not self.do_eval:
+      enc = py_utils.DeterministicDropout(enc, 1.0 - p.dropout_prob)
+      pred = py_utils.DeterministicDropout(pred, 1.0 - p.dropout_prob)
+    enc_p = self.enc_proj.FProp(theta.enc_proj, enc)        # [B, T', J]
+    pred_p = self.pred_proj.FProp(theta.pred_proj, pred)    # [B, U+1, J]
+    logits = self._Joint(theta, enc_p[:, :, None], pred_p[:, None])
+    return NestedMap(logits=logits, paddings=enc_paddings)
+
+  def ComputeLoss(self, theta: NestedMap, predictions: NestedMap,
+                  targets: NestedMap):
+    """Mean nll over the valid utterances. No host sync: the whole loss
+    captures into a hipGraph."""
+    from lingvo_amd.ops import rnnt as rnnt_ops
+    p = self.p
+    logit_lengths = py_utils.LengthsFromPaddings(predictions.paddings)
+    label_lengths = py_utils.LengthsFromPaddings(targets.paddings)
+    nll, valid = rnnt_ops.rnnt_loss(
+        predictions.logits.contiguous(), logit_lengths, targets.ids.long(),
+        label_lengths, blank_id=p.blank_id, impl=p.rnnt_impl)
+    nll = nll.float()
+    valid = valid.float()
+    num_valid = valid.sum()
+    total = (nll * valid).sum()
+    num_labels = (label_lengths.float() * valid).sum()
+    metrics = NestedMap(
+        loss=(total / num_valid.clamp(min=1.0), num_valid),
+        log_pplx=(total.detach() / num_labels.clamp(min=1.0), num_labels),
+        rnnt_valid_fraction=(valid.mean(),
+                             torch.tensor(float(valid.shape[0]))))
+    return metrics, NestedMap(per_example_xent=nll)
+
+  def GreedyDecode(self, theta: NestedMap, enc: torch.Tensor,
+                   enc_paddings: torch.Tensor, max_len: int = 0,
+                   sos_id: int = 1, eos_id: int = 2,
+                   fusion=None) -> torch.Tensor:
+    """Time-synchronous greedy decode, batched and mask-driven: at each
+    frame up to max_symbols_per_frame joint evaluations; a row emits while
+    its argmax is not the blank and the frame is unpadded, and the
+    prediction network advances only for the rows that emitted. Returns
+    [B, T' * max_symbols_per_frame] long, left-packed, padded with 0.
+    Static shapes and no host sync. max_len/sos_id/eos_id are accepted for
+    AsrDecoder's signature and unused."""
+    del max_len, sos_id, eos_id
+    if fusion is not None:
+      raise NotImplementedError(
+          'TransducerDecoder.GreedyDecode: LM shallow fusion is not built '
+          'for the transducer')
+    p = self.p
+    b, t = enc.shape[0], enc.shape[1]
+    width = t * p.max_symbols_per_frame
+    dev = enc.device
+    if t == 0:
+      return torch.zeros(b, 0, dtype=torch.long, device=dev)
+    enc_p = self.enc_proj.FProp(theta.enc_proj, enc.to(self.fprop_dtype))
+    keep = enc_paddings < 0.5                               # [B, T']
+    blank = torch.full((b,), p.blank_id, dtype=torch.long, device=dev)
+    out, states = self._PredictionStep(theta, blank,
+                                       self._InitStates(b, dev))
+    pred_p = self.pred_proj.FProp(theta.pred_proj, out)
+    hyp = torch.zeros(b, width + 1, dtype=torch.long, device=dev)
+    count = torch.zeros(b, dtype=torch.long, device=dev)
+    for i in range(t):
+      go = keep[:, i]
+      for _ in range(p.max_symbols_per_frame):
+        tok = self._Joint(theta, enc_p[:, i], pred_p).argmax(-1)
+        go = go & (tok != p.blank_id)
+        # Rows that do not emit write into the spare last column.
+        hyp.scatter_(1, torch.where(go, count,
+                                    torch.full_like(count, width))[:, None],
+                     torch.where(go, tok, torch.zeros_like(tok))[:, None])
+        count = count + go.long()
+        out, new_states = self._PredictionStep(
+            theta, torch.where(go, tok, blank), states)
+        new_pred_p = self.pred_proj.FProp(theta.pred_proj, out)
+        sel = go[:, None]
+        pred_p = torch.where(sel, new_pred_p, pred_p)
+        states = [NestedMap(c=torch.where(sel, n.c, s.c),
+                            m=torch.where(sel, n.m, s.m))
+                  for n, s in zip(new_states, states)]
+    return hyp[:, :width].contiguous()
+
+  def BeamSearchDecode(self, theta: NestedMap, enc: torch.Tensor,
+                       enc_paddings: torch.Tensor, num_hyps: int = 8,
+                       max_steps: int = 100,
+                       length_norm: float = 0.0) -> NestedMap:
+    raise NotImplementedError(
+        'TransducerDecoder.BeamSearchDecode: transducer beam search is not '
+        'built; use GreedyDecode (decode_num_hyps=1)')
+
+
 class ShallowFusion:
   """LM shallow fusion for decoding (reference tasks/asr/fusion.py):
   combined score = log p_am + weight * log p_lm, with the LM advanced

@@ -166,6 +166,40 @@ class Librispeech960ConformerSCtc(Librispeech960ConformerS):
     return p
 
 
+def _TransducerHead(task_p, joint_dim, rnn_cell_dim):
+  """Replaces the attention decoder of `task_p` with a transducer decoder
+  (one-layer LSTM prediction network + joint network) of the same
+  vocabulary over the same encoder outputs."""
+  old = task_p.decoder
+  task_p.decoder = asr_model.TransducerDecoder.Params().Set(
+      vocab_size=old.vocab_size, emb_dim=old.emb_dim,
+      rnn_cell_dim=rnn_cell_dim, num_lstm_layers=1,
+      source_dim=old.source_dim, joint_dim=joint_dim,
+      dropout_prob=old.dropout_prob)
+  return task_p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960WpmConformerLTransducer(Librispeech960WpmConformerL):
+  """Conformer-L transducer: the north-star encoder, learner and input with
+  a TransducerDecoder (prediction network 1x640, joint 640, emb 128)."""
+
+  def Task(self):
+    p = _TransducerHead(super().Task(), joint_dim=640, rnn_cell_dim=640)
+    p.name = 'librispeech_conformer_l_transducer'
+    return p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960ConformerSTransducer(Librispeech960ConformerS):
+  """Conformer-S transducer: quick tests."""
+
+  def Task(self):
+    p = _TransducerHead(super().Task(), joint_dim=256, rnn_cell_dim=320)
+    p.name = 'librispeech_conformer_s_transducer'
+    return p
+
+
 @registry.RegisterSingleTaskModel
 class Librispeech960WpmConformerLJointCtc(Librispeech960WpmConformerL):
   """Joint CTC/attention Conformer-L: the attention decoder plus an

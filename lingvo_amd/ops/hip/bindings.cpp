@@ -164,6 +164,20 @@ torch::Tensor ctc_bwd(torch::Tensor logits, torch::Tensor logit_lengths,
                       torch::Tensor gout, int64_t blank);
 int64_t ctc_max_label_len();
 
+// rnnt.hip
+std::vector<torch::Tensor> rnnt_fwd(torch::Tensor logits,
+                                    torch::Tensor logit_lengths,
+                                    torch::Tensor labels,
+                                    torch::Tensor label_lengths,
+                                    int64_t blank);
+torch::Tensor rnnt_bwd(torch::Tensor logits, torch::Tensor logit_lengths,
+                       torch::Tensor labels, torch::Tensor label_lengths,
+                       torch::Tensor lse, torch::Tensor emis,
+                       torch::Tensor alpha, torch::Tensor beta,
+                       torch::Tensor valid, torch::Tensor gnll,
+                       int64_t blank);
+int64_t rnnt_max_label_len();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   RegisterInputPipeline(m);
   RegisterWpmTokenizer(m);
@@ -217,6 +231,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ctc_bwd", &ctc_bwd, "CTC loss backward: dlogits");
   m.def("ctc_max_label_len", &ctc_max_label_len,
         "Largest label width L the CTC kernels support");
+  m.def("rnnt_fwd", &rnnt_fwd,
+        "Transducer loss forward: nll, valid and the backward's workspaces");
+  m.def("rnnt_bwd", &rnnt_bwd, "Transducer loss backward: dlogits");
+  m.def("rnnt_max_label_len", &rnnt_max_label_len,
+        "Largest label width U the transducer kernels support");
   m.def("s2d_fwd", &s2d_fwd, "Space-to-depth + pad (conv frontend)");
   m.def("topk_rows", &topk_rows, "Row-wise top-k (beam pruning, K12)");
   m.def("s2d_inv", &s2d_inv, "Inverse space-to-depth");

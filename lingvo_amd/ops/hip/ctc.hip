@@ -32,6 +32,7 @@
 #include <torch/extension.h>
 
 #include "common.h"
+#include "lse_rows.h"
 
 namespace {
 
@@ -40,38 +41,6 @@ constexpr int kRowWaves = 4;    // rows per workgroup in the row pass
 constexpr int kGradThreads = 256;
 constexpr float kNeg = -1e30f;
 constexpr float kNegTest = -1e29f;
-
-// dtype helpers: 16-byte vectors of logits.
-template <typename T>
-struct Elem;
-
-template <>
-struct Elem<float> {
-  static constexpr int kVec = 4;
-  typedef floatx4 Vec;
-  static __device__ __forceinline__ float ToFloat(float x) { return x; }
-  static __device__ __forceinline__ float FromFloat(float x) { return x; }
-};
-
-template <>
-struct Elem<unsigned short> {  // bf16 bits
-  static constexpr int kVec = 8;
-  typedef ushortx8 Vec;
-  static __device__ __forceinline__ float ToFloat(unsigned short x) {
-    return bf16_bits_to_float(x);
-  }
-  static __device__ __forceinline__ unsigned short FromFloat(float x) {
-    return float_to_bf16_bits(x);
-  }
-};
-
-// Elements before the first 16-byte boundary of row pointer p (<= n).
-template <typename T>
-__device__ __forceinline__ int HeadElems(const T* p, int n) {
-  const int mis = (int)(reinterpret_cast<uintptr_t>(p) & 15);
-  const int head = mis ? (16 - mis) / (int)sizeof(T) : 0;
-  return head < n ? head : n;
-}
 
 // Lengths of utterance b, zeroed when either is out of range.
 __device__ __forceinline__ bool RowLengths(const long* in_len,
@@ -83,14 +52,6 @@ __device__ __forceinline__ bool RowLengths(const long* in_len,
   *tb = ok ? (int)t : 0;
   *lb = ok ? (int)l : 0;
   return ok;
-}
-
-__device__ __forceinline__ void OnlineLse(float f, float& m, float& s) {
-  if (f > m) {
-    s *= expf(m - f);
-    m = f;
-  }
-  s += expf(f - m);
 }
 
 // ---- pass 1: lse + emission table -----------------------------------------
