@@ -26,13 +26,15 @@ from lingvo_amd.ops import fusion
 def _ref_attention(q, k, v, klen, bias, win_l, win_r, bias_clip, scale,
                    q_segment_ids=None, k_segment_ids=None,
                    chunk_size=0, left_chunks=0):
-  """fp32 reference with identical semantics (any backend)."""
+  """fp32 reference with identical semantics (any backend); float64
+  inputs are computed in float64."""
   B, T, N, H = q.shape
   S, NKV = k.shape[1], k.shape[2]
   group = N // NKV
-  qf = q.float().permute(0, 2, 1, 3)  # [B,N,T,H]
-  kf = k.float().permute(0, 2, 1, 3)
-  vf = v.float().permute(0, 2, 1, 3)
+  ft = torch.float64 if q.dtype == torch.float64 else torch.float32
+  qf = q.to(ft).permute(0, 2, 1, 3)  # [B,N,T,H]
+  kf = k.to(ft).permute(0, 2, 1, 3)
+  vf = v.to(ft).permute(0, 2, 1, 3)
   if group > 1:
     kf = kf.repeat_interleave(group, dim=1)
     vf = vf.repeat_interleave(group, dim=1)
@@ -41,7 +43,7 @@ def _ref_attention(q, k, v, klen, bias, win_l, win_r, bias_clip, scale,
   kpos = torch.arange(S, device=q.device)[None, :]
   if bias is not None:
     d = (qpos - kpos).clamp(-bias_clip, bias_clip) + bias_clip
-    logits = logits + bias.float()[:, d]  # [N,T,S] broadcast over B
+    logits = logits + bias.to(ft)[:, d]  # [N,T,S] broadcast over B
   mask = torch.ones(T, S, dtype=torch.bool, device=q.device)
   if win_l >= 0:
     mask &= kpos >= qpos - win_l
@@ -69,12 +71,13 @@ class _FlashAttnFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, q, k, v, klen, bias, qseg, kseg, win_l, win_r,
-              bias_clip, scale, chunk_size, left_chunks):
+              bias_clip, scale, chunk_size, left_chunks, bwd_route='auto'):
     ext = _loader.get_ext(required=True)
     bias_b = None if bias is None else bias.to(torch.bfloat16).contiguous()
     o, lse = ext.fa_fwd(q, k, v, klen, bias_b, qseg, kseg, win_l, win_r,
                         bias_clip, scale, chunk_size, left_chunks)
     empty = torch.empty(0)
+    ctx.bwd_route = bwd_route
     ctx.save_for_backward(q, k, v, o, lse,
                           klen if klen is not None else empty,
                           bias_b if bias_b is not None else empty,
@@ -98,10 +101,10 @@ class _FlashAttnFn(torch.autograd.Function):
     dq, dk, dv, dbias = ext.fa_bwd(
         dout.contiguous(), q, k, v, o, lse, klen, bias_b, qseg, kseg,
         bias_grad, win_l, win_r, bias_clip, scale, chunk_size,
-        left_chunks)
+        left_chunks, route=ctx.bwd_route)
     dbias_out = dbias.to(bias_dtype) if bias_grad else None
     return (dq, dk, dv, None, dbias_out, None, None, None, None, None,
-            None, None, None)
+            None, None, None, None)
 
 
 class _FlashAttnPackedFn(torch.autograd.Function):
@@ -116,8 +119,9 @@ class _FlashAttnPackedFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, qkv, n, h, klen, bias, qseg, kseg, win_l, win_r,
-              bias_clip, scale, chunk_size, left_chunks):
+              bias_clip, scale, chunk_size, left_chunks, bwd_route='auto'):
     ext = _loader.get_ext(required=True)
+    ctx.bwd_route = bwd_route
     bias_b = None if bias is None else bias.to(torch.bfloat16).contiguous()
     q, k, v = _FlashAttnPackedFn._views(qkv, n, h)
     o, lse = ext.fa_fwd(q, k, v, klen, bias_b, qseg, kseg, win_l, win_r,
@@ -149,10 +153,10 @@ class _FlashAttnPackedFn(torch.autograd.Function):
     dbias = ext.fa_bwd(
         dout.contiguous(), q, k, v, o, lse, klen, bias_b, qseg, kseg,
         bias_grad, win_l, win_r, bias_clip, scale, chunk_size,
-        left_chunks, dq, dk, dv)[3]
+        left_chunks, dq, dk, dv, ctx.bwd_route)[3]
     dbias_out = dbias.to(bias_dtype) if bias_grad else None
     return (dqkv, None, None, None, dbias_out, None, None, None, None,
-            None, None, None, None)
+            None, None, None, None, None)
 
 
 def flash_attention_packed(qkv: torch.Tensor, num_heads: int,
@@ -163,11 +167,12 @@ def flash_attention_packed(qkv: torch.Tensor, num_heads: int,
                            scale: Optional[float] = None,
                            q_segment_ids: Optional[torch.Tensor] = None,
                            k_segment_ids: Optional[torch.Tensor] = None,
-                           chunk_size: int = 0, left_chunks: int = 0
-                           ) -> torch.Tensor:
+                           chunk_size: int = 0, left_chunks: int = 0,
+                           bwd_route: str = 'auto') -> torch.Tensor:
   """flash_attention on a packed self-attention projection: qkv is
   [B,T,3*N*H] bf16 CUDA laid out [q | k | v] with N == NKV == num_heads.
-  Returns o [B,T,N,H]; the gradient is one [B,T,3*N*H] tensor."""
+  Returns o [B,T,N,H]; the gradient is one [B,T,3*N*H] tensor.
+  bwd_route forces the backward kernel (see flash_attention)."""
   assert qkv.is_cuda and qkv.dtype == torch.bfloat16
   assert qkv.shape[-1] % (3 * num_heads) == 0
   h = qkv.shape[-1] // (3 * num_heads)
@@ -181,7 +186,7 @@ def flash_attention_packed(qkv: torch.Tensor, num_heads: int,
   return _FlashAttnPackedFn.apply(
       qkv.contiguous(), num_heads, h, klen, bias, q_segment_ids,
       k_segment_ids, win_l, win_r, bias_clip, scale, chunk_size,
-      left_chunks)
+      left_chunks, bwd_route)
 
 
 def _meets_stride_contract(t: torch.Tensor) -> bool:
@@ -213,11 +218,15 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     scale: Optional[float] = None,
                     q_segment_ids: Optional[torch.Tensor] = None,
                     k_segment_ids: Optional[torch.Tensor] = None,
-                    chunk_size: int = 0, left_chunks: int = 0
-                    ) -> torch.Tensor:
+                    chunk_size: int = 0, left_chunks: int = 0,
+                    bwd_route: str = 'auto') -> torch.Tensor:
   """q [B,T,N,H], k/v [B,S,NKV,H] -> [B,T,N,H]. Optional packed-input
   segment ids [B,T]/[B,S]: attention is blocked across segments
-  (reference PackSequences segment_ids consumed by the mask path)."""
+  (reference PackSequences segment_ids consumed by the mask path).
+
+  bwd_route picks the GPU backward kernel: 'auto' (by shape), 'tiles'
+  (one workgroup per 128-key tile, dQ through fp32 atomics) or 'fused'
+  (one workgroup per head; raises where the shape does not qualify)."""
   if scale is None:
     scale = 1.0 / math.sqrt(q.shape[-1])
   if klen is not None:
@@ -230,7 +239,7 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     out = _FlashAttnFn.apply(
         _kernel_input(q), _kernel_input(k), _kernel_input(v), klen, bias,
         q_segment_ids, k_segment_ids, win_l, win_r, bias_clip, scale,
-        chunk_size, left_chunks)
+        chunk_size, left_chunks, bwd_route)
     return out.to(orig) if orig != torch.bfloat16 else out
   out = _ref_attention(q, k, v, klen, bias, win_l, win_r, bias_clip, scale,
                        q_segment_ids, k_segment_ids, chunk_size,

@@ -41,7 +41,8 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
                                   int64_t left_chunks,
                                   c10::optional<torch::Tensor> dq_out,
                                   c10::optional<torch::Tensor> dk_out,
-                                  c10::optional<torch::Tensor> dv_out);
+                                  c10::optional<torch::Tensor> dv_out,
+                                  const std::string& route);
 
 // conv1d.hip
 torch::Tensor dwconv1d_fwd(torch::Tensor x, torch::Tensor w,
@@ -208,7 +209,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("win_r"), py::arg("bias_clip"), py::arg("scale"),
         py::arg("chunk_size"), py::arg("left_chunks"),
         py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
-        py::arg("dv_out") = py::none());
+        py::arg("dv_out") = py::none(), py::arg("route") = "auto");
   m.def("emb_gather", &emb_gather, "Embedding gather fwd");
   m.def("emb_scatter_add", &emb_scatter_add,
         "Deterministic embedding scatter-add bwd");

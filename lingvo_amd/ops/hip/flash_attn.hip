@@ -9,11 +9,24 @@
 //    transposed [H][64]; online softmax in fp32 with per-row (m, l)
 //    tracked in the 16-lane C-layout groups; P routed through per-wave
 //    LDS for the PV MFMA. Saves LSE for backward.
-//  - bwd: grid (ceil(S/64), N_kv, B); each block owns a 64-key tile,
-//    loops q-heads of the GQA group and q-tiles; recomputes P^T from
-//    LSE; accumulates dK/dV in registers (written once, no atomics);
-//    dQ accumulated via fp32 global atomics; optional clipped
-//    rel-position bias gradient via LDS accumulation.
+//  - bwd, two routes chosen on the host from shapes only:
+//    'fused' (fa_bwd_fused_kernel): self-attention with N == NKV, H == 64,
+//    T == S <= 384, no segment ids or chunkwise mask. Grid (N, B), one
+//    workgroup of 8 waves per head; strips of 16 keys live across the
+//    waves with K/V fragments and dK/dV accumulators in registers; the
+//    32-row q-tiles are walked once, loads for the next tile in flight;
+//    delta = rowsum(dO*O) is reduced while dO is staged; dQ is contracted
+//    over all keys from a [32][S_pad] dS tile in LDS, rounded once and
+//    stored as bf16; the bias gradient leaves as one fp32 row per
+//    workgroup, summed over B by fa_dbias_reduce. No atomics, no fp32 dQ
+//    buffer, fixed summation order.
+//    'tiles' (fa_bwd_delta + fa_bwd_kernel + fa_dq_cast): every other
+//    shape. Grid (ceil(S/128), N_kv, B), 8 waves; each block owns a
+//    128-key tile, loops q-heads of the GQA group and 64-row q-tiles;
+//    recomputes P^T from LSE; dK/dV in registers (written once; fp32
+//    atomics across the heads of a GQA group); dQ accumulated through
+//    fp32 global atomics into a zero-filled buffer and cast afterwards;
+//    clipped rel-position bias gradient via LDS then global atomics.
 //
 // Masks: key k is visible from query q iff
 //   k < klen[b]  AND  (win_l < 0 OR k >= q - win_l)
@@ -374,23 +387,29 @@ __global__ __launch_bounds__(FWD_BLOCK) void fa_fwd_kernel(
 // Backward: delta = rowsum(dO * O)
 // ---------------------------------------------------------------------------
 template <int H>
-__global__ void fa_bwd_delta(const unsigned short* __restrict__ dout,
-                             const unsigned short* __restrict__ o,
-                             float* __restrict__ delta, int B, int T, int N) {
-  // One wave per (b, t, n) row.
-  const long row = (long)blockIdx.x * NW + threadIdx.x / WAVE_SIZE;
-  const int lane = threadIdx.x & 63;
-  if (row >= (long)B * T * N) return;
-  // row enumerates (b, t, n) in memory order of [B,T,N,H].
-  const unsigned short* dp = dout + row * H;
-  const unsigned short* op = o + row * H;
+__global__ __launch_bounds__(BLOCK) void fa_bwd_delta(
+    const unsigned short* __restrict__ dout,
+    const unsigned short* __restrict__ o, float* __restrict__ delta, int B,
+    int T, int N) {
+  // H/8 neighbouring lanes per (b, t, n) row, one 16-byte load of dO and
+  // of O each; rows enumerate [B,T,N,H] in memory order.
+  constexpr int LPR = H / 8;           // lanes per row
+  constexpr int RPB = BLOCK / LPR;     // rows per block
+  const long nrows = (long)B * T * N;
+  const long row = (long)blockIdx.x * RPB + threadIdx.x / LPR;
+  const int c = threadIdx.x % LPR;
+  // Clamped row: whole waves stay in the shuffles below.
+  const long lrow = row < nrows ? row : nrows - 1;
+  const ushortx8 dv8 =
+      *reinterpret_cast<const ushortx8*>(dout + lrow * H + c * 8);
+  const ushortx8 ov8 = *reinterpret_cast<const ushortx8*>(o + lrow * H + c * 8);
   float sum = 0.f;
 #pragma unroll
-  for (int i = lane; i < H; i += WAVE_SIZE) {
-    sum += bf16_bits_to_float(dp[i]) * bf16_bits_to_float(op[i]);
-  }
-  sum = wave_reduce_sum(sum);
-  if (lane == 0) {
+  for (int j = 0; j < 8; ++j)
+    sum += bf16_bits_to_float(dv8[j]) * bf16_bits_to_float(ov8[j]);
+#pragma unroll
+  for (int off = 1; off < LPR; off <<= 1) sum += __shfl_xor(sum, off);
+  if (c == 0 && row < nrows) {
     long b = row / ((long)T * N);
     long tn = row % ((long)T * N);
     long t = tn / N, n = tn % N;
@@ -794,11 +813,453 @@ __global__ void fa_dq_cast(const float* __restrict__ dq_acc,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Backward, fused route: one workgroup per (head, batch), self-attention
+// with N == NKV and T == S <= NWF * SPW * 16.
+//
+// Keys across waves: strip s (16 keys) belongs to wave s % NWF, which keeps
+// the strip's K/V A-fragments and dK/dV accumulators in registers for the
+// whole kernel. The q-tiles are walked once. Per tile every wave writes its
+// dS strips into one [QTB][S_pad] LDS tile; after a barrier dQ^T = K^T dS^T
+// is computed over the whole key range (K^T resident in LDS), rounded once
+// and stored as bf16 straight into dq. delta = rowsum(dO * O) is reduced
+// while the dO tile is staged. Global loads for tile i+1 are issued into
+// registers before the MFMAs of tile i. The bias-gradient diagonals are
+// summed in LDS by one owning thread each (fixed order, no atomics) and
+// leave as one fp32 row per workgroup for fa_dbias_reduce.
+// ---------------------------------------------------------------------------
+template <int NWF, int SPW>
+constexpr int fused_max_s() { return NWF * SPW * 16; }
+
+// Dynamic LDS bytes of fa_bwd_fused_kernel (H == 64).
+template <int QTB, int NWF, int SPW>
+static size_t fused_lds_bytes(bool has_bias, bool bias_grad, int nbias) {
+  constexpr int H = 64;
+  constexpr int SP = fused_max_s<NWF, SPW>();
+  return (size_t)QTB * H * 2 * 2           // q_lds + do_lds
+         + (size_t)H * 128 * 2             // qt_lds + dot_lds (128B pitch)
+         + (size_t)H * SP * 2              // kt_lds
+         + (size_t)QTB * SP * 2            // ds_lds
+         + (size_t)NWF * 16 * 128          // a_lds (128B pitch)
+         + 2 * QTB * sizeof(float)         // lse_s + delta_s
+         + (has_bias ? nbias * sizeof(float) : 0)
+         + (bias_grad ? (2 * SP + QTB) * sizeof(float) : 0);
+}
+
+template <int H, bool BIAS_GRAD, int QTB, int NWF, int SPW>
+__global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
+    const unsigned short* __restrict__ dout,
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
+    const unsigned short* __restrict__ v, const unsigned short* __restrict__ o,
+    const float* __restrict__ lse, const int* __restrict__ klen_ptr,
+    const unsigned short* __restrict__ bias,
+    unsigned short* __restrict__ dq, unsigned short* __restrict__ dk,
+    unsigned short* __restrict__ dv,
+    float* __restrict__ dbias_part,            // [B][N][nbias] if BIAS_GRAD
+    int T, int N, int win_l, int win_r, int bias_clip, float scale,
+    long sq, long sk, long sv, long sdq, long sdk, long sdv) {
+  static_assert(H == 64, "fused backward is built for H == 64");
+  constexpr int NT = NWF * WAVE_SIZE;
+  constexpr int SP = fused_max_s<NWF, SPW>();  // padded key count
+  constexpr int ROWB = H * 2;
+  constexpr int KH = H / 32;
+  constexpr int HF = H / 16;
+  constexpr int NQ = QTB / 16;
+  constexpr int TP = 128;        // pitch of the [..][QTB] tiles (swizzle span)
+  constexpr int DSP = SP * 2;    // pitch of the [..][SP] tiles
+  constexpr int NDACC = 2 * SP + QTB;
+  constexpr int STG = QTB * (ROWB / 16);       // staging threads (16B each)
+  static_assert(SP % 64 == 0, "[..][SP] rows must span whole swizzle blocks");
+  static_assert((NWF * SPW) % 2 == 0, "dQ contracts over pairs of strips");
+  static_assert(QTB <= 64 && QTB % 16 == 0 && STG <= NT, "q-tile shape");
+  // dQ^T output tiles (QTB/16 x H/16) over the waves; a wave's tiles share
+  // their dS B-fragment.
+  constexpr int NTILE = NQ * HF;
+  constexpr int TPW = (NTILE + NWF - 1) / NWF;
+  static_assert(HF % TPW == 0, "a wave's dQ tiles must share one q strip");
+
+  const int nbias = 2 * bias_clip + 1;
+  extern __shared__ char smem[];
+  char* q_lds = smem;                        // [QTB][H] swz
+  char* do_lds = q_lds + QTB * ROWB;         // [QTB][H] swz
+  char* qt_lds = do_lds + QTB * ROWB;        // [H][QTB] swz, pitch TP
+  char* dot_lds = qt_lds + H * TP;           // [H][QTB] swz, pitch TP
+  char* kt_lds = dot_lds + H * TP;           // [H][SP] swz
+  char* ds_lds = kt_lds + H * DSP;           // [QTB][SP] swz
+  char* a_lds = ds_lds + QTB * DSP;          // [NWF][16][QTB] swz, pitch TP
+  float* lse_s = (float*)(a_lds + NWF * 16 * TP);       // [QTB]
+  float* delta_s = lse_s + QTB;                         // [QTB]
+  float* bias_s = delta_s + QTB;                        // [nbias] if bias
+  // Unclipped per-diagonal sums, slot = (q - key) + SP - 1.
+  float* dacc = bias_s + (bias ? nbias : 0);            // [NDACC] if BIAS_GRAD
+
+  const int n = blockIdx.x;
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int wid = tid / WAVE_SIZE;
+  const int lane = tid & 63;
+  const int g = lane >> 4;
+  const int cl = lane & 15;
+  const int S = T;
+  const int klen = klen_ptr ? min(max(klen_ptr[b], 0), S) : S;
+  const int nact = (klen + 15) / 16;          // strips with a visible key
+  const int kact = ((nact + 1) & ~1) * 16;    // dQ contraction length
+  const int nqt = (T + QTB - 1) / QTB;
+  // Window half-widths with "no limit" folded in (T <= SP keeps the sums
+  // far from overflow).
+  const int wl = win_l < 0 ? 0x3fffffff : win_l;
+  const int wr = win_r < 0 ? 0x3fffffff : win_r;
+
+  // Staging role of this thread: 16 bytes of one q/dO/O row; the last QTB
+  // threads carry lse.
+  const int srow = tid / (ROWB / 16);
+  const int sc = tid % (ROWB / 16);
+  const bool stager = tid < STG;
+  const int lrow = tid - (NT - QTB);
+  ushortx8 pq, pdo, po;
+  float plse = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pq[j] = pdo[j] = po[j] = 0;
+
+  // Clamped row, select at commit time: the loads stay unconditional so
+  // they can be in flight across the MFMAs of the previous tile.
+  auto prefetch = [&](int qb) {
+    if (stager) {
+      const long tok = (long)b * T + min(qb + srow, T - 1);
+      pq = *reinterpret_cast<const ushortx8*>(q + tok * sq + n * H + sc * 8);
+      pdo = *reinterpret_cast<const ushortx8*>(dout + (tok * N + n) * H +
+                                               sc * 8);
+      po = *reinterpret_cast<const ushortx8*>(o + (tok * N + n) * H + sc * 8);
+    }
+    if (lrow >= 0)
+      plse = lse[((long)b * N + n) * T + min(qb + lrow, T - 1)];
+  };
+  prefetch(0);
+
+  // One-time LDS setup: dS tile zeroed (columns of the odd padding strip
+  // are read by dQ but never written), bias row, diagonal sums, K^T.
+  for (int i = tid; i < QTB * DSP / 16; i += NT) {
+    ushortx8 z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = 0;
+    *reinterpret_cast<ushortx8*>(ds_lds + i * 16) = z;
+  }
+  if (bias) {
+    for (int i = tid; i < nbias; i += NT)
+      bias_s[i] = bf16_bits_to_float(bias[(long)n * nbias + i]);
+  }
+  if (BIAS_GRAD) {
+    for (int i = tid; i < NDACC; i += NT) dacc[i] = 0.f;
+  }
+  for (int i = tid; i < kact * (H / 8); i += NT) {
+    const int key = i / (H / 8);
+    const int h0 = (i % (H / 8)) * 8;
+    ushortx8 kv = *reinterpret_cast<const ushortx8*>(
+        k + ((long)b * S + min(key, klen - 1)) * sk + n * H + h0);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int h = h0 + j;
+      *reinterpret_cast<unsigned short*>(kt_lds + h * DSP + swz(h, key * 2)) =
+          key < klen ? kv[j] : (unsigned short)0;
+    }
+  }
+
+  // K, V fragments (A layout) and accumulators of this wave's strips.
+  bf16x8 kfrag[SPW][KH], vfrag[SPW][KH];
+  f32x4 acc_dk[SPW][HF], acc_dv[SPW][HF];
+#pragma unroll
+  for (int si = 0; si < SPW; ++si) {
+    const int key = (wid + si * NWF) * 16 + cl;
+    const bool ok = key < klen;
+#pragma unroll
+    for (int kk = 0; kk < KH; ++kk) {
+      if (ok) {
+        const long tok = (long)b * S + key;
+        const int col = n * H + kk * 32 + g * 8;
+        kfrag[si][kk] = load_bf16x8_bits(k + tok * sk + col);
+        vfrag[si][kk] = load_bf16x8_bits(v + tok * sv + col);
+      } else {
+        float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        kfrag[si][kk] = pack_bf16x8(z);
+        vfrag[si][kk] = pack_bf16x8(z);
+      }
+    }
+#pragma unroll
+    for (int hf = 0; hf < HF; ++hf) {
+      acc_dk[si][hf] = {0.f, 0.f, 0.f, 0.f};
+      acc_dv[si][hf] = {0.f, 0.f, 0.f, 0.f};
+    }
+  }
+
+  char* aw = a_lds + wid * 16 * TP;
+  for (int qt = 0; qt < nqt; ++qt) {
+    const int qb = qt * QTB;
+    // No barrier here: q/dO/lse/delta were last read before the barrier
+    // that ends the strip phase, and the dS tile and dacc are next written
+    // after the barrier below.
+    if (stager) {
+      const bool ok = qb + srow < T;
+      float part = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        pq[j] = ok ? pq[j] : (unsigned short)0;
+        pdo[j] = ok ? pdo[j] : (unsigned short)0;
+        part += bf16_bits_to_float(pdo[j]) * bf16_bits_to_float(po[j]);
+      }
+      *reinterpret_cast<ushortx8*>(q_lds + srow * ROWB + swz(srow, sc * 16)) =
+          pq;
+      *reinterpret_cast<ushortx8*>(do_lds + srow * ROWB +
+                                   swz(srow, sc * 16)) = pdo;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int h = sc * 8 + j;
+        *reinterpret_cast<unsigned short*>(qt_lds + h * TP +
+                                           swz(h, srow * 2)) = pq[j];
+        *reinterpret_cast<unsigned short*>(dot_lds + h * TP +
+                                           swz(h, srow * 2)) = pdo[j];
+      }
+      // delta: the row's ROWB/16 = 8 threads are neighbouring lanes.
+#pragma unroll
+      for (int off = 1; off < ROWB / 16; off <<= 1)
+        part += __shfl_xor(part, off);
+      if (sc == 0) delta_s[srow] = part;
+    }
+    if (lrow >= 0) lse_s[lrow] = qb + lrow < T ? plse : NEG_INF;
+    __syncthreads();
+    if (qt + 1 < nqt) prefetch(qb + QTB);
+
+#pragma unroll
+    for (int si = 0; si < SPW; ++si) {
+      const int strip = wid + si * NWF;
+      if (strip >= nact) continue;   // wave-uniform
+      const int k0 = strip * 16;
+      // S^T strip: rows = 16 keys, cols = QTB queries.
+      float pt[NQ][4];   // P^T
+      float dlg[NQ][4];  // dLogits
+#pragma unroll
+      for (int nf = 0; nf < NQ; ++nf) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < KH; ++kk) {
+          bf16x8 bq =
+              lds_frag(q_lds, nf * 16 + cl, ROWB, (kk * 32 + g * 8) * 2);
+          acc = mfma16x16x32_bf16(kfrag[si][kk], bq, acc);
+        }
+        const int qcol = qb + nf * 16 + cl;
+        const float l = lse_s[nf * 16 + cl];
+        const bool lok = (qcol < T) & (l > NEG_INF * 0.5f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = k0 + g * 4 + r;
+          float val = acc[r] * scale;
+          if (bias) {
+            int d = qcol - key;
+            d = d < -bias_clip ? -bias_clip : (d > bias_clip ? bias_clip : d);
+            val += bias_s[d + bias_clip];
+          }
+          // visible() without its early returns: one select per element
+          // instead of a branch tree.
+          const bool vis = (key < klen) & (key >= qcol - wl) &
+                           (key <= qcol + wr) & lok;
+          pt[nf][r] = vis ? __expf(val - l) : 0.f;
+        }
+      }
+
+      // P^T -> a_lds; dV += P^T @ dO (B from dOt).
+#pragma unroll
+      for (int nf = 0; nf < NQ; ++nf) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          int row = g * 4 + r;
+          int col = nf * 16 + cl;
+          *reinterpret_cast<unsigned short*>(
+              aw + row * TP + swz(row, col * 2)) =
+              float_to_bf16_bits(pt[nf][r]);
+        }
+      }
+#pragma unroll
+      for (int kk2 = 0; kk2 < QTB / 32; ++kk2) {
+        bf16x8 pa = lds_frag(aw, cl, TP, (kk2 * 32 + g * 8) * 2);
+#pragma unroll
+        for (int hf = 0; hf < HF; ++hf) {
+          bf16x8 bd =
+              lds_frag(dot_lds, hf * 16 + cl, TP, (kk2 * 32 + g * 8) * 2);
+          acc_dv[si][hf] = mfma16x16x32_bf16(pa, bd, acc_dv[si][hf]);
+        }
+      }
+
+      // dP^T = V @ dO^T (B from do_lds rows).
+#pragma unroll
+      for (int nf = 0; nf < NQ; ++nf) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < KH; ++kk) {
+          bf16x8 bd =
+              lds_frag(do_lds, nf * 16 + cl, ROWB, (kk * 32 + g * 8) * 2);
+          acc = mfma16x16x32_bf16(vfrag[si][kk], bd, acc);
+        }
+        const float dl = delta_s[nf * 16 + cl];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dlg[nf][r] = pt[nf][r] * (acc[r] - dl);
+      }
+
+      // dS^T (scaled, bf16) -> a_lds (overwrite) and, transposed, into the
+      // shared dS tile: a lane's 4 keys are 8 contiguous bytes of row q.
+#pragma unroll
+      for (int nf = 0; nf < NQ; ++nf) {
+        ushortx4 pk;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          int row = g * 4 + r;
+          int col = nf * 16 + cl;
+          pk[r] = float_to_bf16_bits(dlg[nf][r] * scale);
+          *reinterpret_cast<unsigned short*>(
+              aw + row * TP + swz(row, col * 2)) = pk[r];
+        }
+        const int qrow = nf * 16 + cl;
+        *reinterpret_cast<ushortx4*>(
+            ds_lds + qrow * DSP + swz(qrow, (k0 + g * 4) * 2)) = pk;
+      }
+      // dK += dS^T @ Q (B = Qt).
+#pragma unroll
+      for (int kk2 = 0; kk2 < QTB / 32; ++kk2) {
+        bf16x8 da = lds_frag(aw, cl, TP, (kk2 * 32 + g * 8) * 2);
+#pragma unroll
+        for (int hf = 0; hf < HF; ++hf) {
+          bf16x8 bq =
+              lds_frag(qt_lds, hf * 16 + cl, TP, (kk2 * 32 + g * 8) * 2);
+          acc_dk[si][hf] = mfma16x16x32_bf16(da, bq, acc_dk[si][hf]);
+        }
+      }
+    }
+    __syncthreads();
+
+    // dQ^T tiles: A = K^T rows (h), B = dS rows (q), contraction over the
+    // active keys. A lane ends with 4 consecutive h of one q row.
+    if (wid * TPW < NTILE) {
+      const int qs = (wid * TPW) / HF;
+      const int hf0 = (wid * TPW) % HF;
+      f32x4 acc_dq[TPW];
+#pragma unroll
+      for (int i = 0; i < TPW; ++i) acc_dq[i] = {0.f, 0.f, 0.f, 0.f};
+      for (int kk2 = 0; kk2 < kact / 32; ++kk2) {
+        bf16x8 bs =
+            lds_frag(ds_lds, qs * 16 + cl, DSP, (kk2 * 32 + g * 8) * 2);
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+          bf16x8 ak = lds_frag(kt_lds, (hf0 + i) * 16 + cl, DSP,
+                               (kk2 * 32 + g * 8) * 2);
+          acc_dq[i] = mfma16x16x32_bf16(ak, bs, acc_dq[i]);
+        }
+      }
+      const int qrow = qb + qs * 16 + cl;
+      if (qrow < T) {
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+          ushortx4 ov;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) ov[r] = float_to_bf16_bits(acc_dq[i][r]);
+          *reinterpret_cast<ushortx4*>(dq + ((long)b * T + qrow) * sdq +
+                                       n * H + (hf0 + i) * 16 + g * 4) = ov;
+        }
+      }
+    }
+    if (BIAS_GRAD) {
+      // One thread per diagonal of the dS tile (entries hold
+      // dlogits*scale; invisible positions are exact zeros), handed out
+      // from the last thread down so the waves without a dQ tile go first.
+      // A slot of dacc has one owner per tile: plain read-modify-write.
+      const int ndiag = QTB + kact - 1;
+      for (int di = NT - 1 - tid; di < ndiag; di += NT) {
+        const int doff = di - (kact - 1);   // qrow - key within the tile
+        const int q_lo = max(0, doff);
+        const int q_hi = min(QTB - 1, kact - 1 + doff);
+        float sum = 0.f;
+        for (int qrow = q_lo; qrow <= q_hi; ++qrow) {
+          const int key = qrow - doff;
+          sum += bf16_bits_to_float(*reinterpret_cast<unsigned short*>(
+              ds_lds + qrow * DSP + swz(qrow, key * 2)));
+        }
+        dacc[qb + doff + SP - 1] += sum;
+      }
+    }
+  }
+
+  // dK/dV: every key row < S of this head is written once; strips past
+  // klen carry zero accumulators.
+#pragma unroll
+  for (int si = 0; si < SPW; ++si) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = (wid + si * NWF) * 16 + g * 4 + r;
+      if (key >= S) continue;
+      const long tok = (long)b * S + key;
+#pragma unroll
+      for (int hf = 0; hf < HF; ++hf) {
+        dk[tok * sdk + n * H + hf * 16 + cl] =
+            float_to_bf16_bits(acc_dk[si][hf][r]);
+        dv[tok * sdv + n * H + hf * 16 + cl] =
+            float_to_bf16_bits(acc_dv[si][hf][r]);
+      }
+    }
+  }
+
+  if (BIAS_GRAD) {
+    // Clip merge in fixed order: wave w sums the dacc slots that clamp to
+    // bias slot i = w, w + NWF, ... (one slot inside, a range at the ends).
+    __syncthreads();
+    const float inv_scale = 1.f / scale;
+    for (int i = wid; i < nbias; i += NWF) {
+      int lo = i == 0 ? 0 : i - bias_clip + SP - 1;
+      int hi = i == nbias - 1 ? NDACC - 1 : i - bias_clip + SP - 1;
+      lo = max(lo, 0);
+      hi = min(hi, NDACC - 1);
+      float sum = 0.f;
+      for (int j = lo + lane; j <= hi; j += WAVE_SIZE) sum += dacc[j];
+      sum = wave_reduce_sum(sum);
+      if (lane == 0)
+        dbias_part[((long)b * N + n) * nbias + i] = sum * inv_scale;
+    }
+  }
+}
+
+// dbias[c] = sum over b of part[b][c], c over N * nbias, in fixed order.
+constexpr int kDbSlices = 16;
+__global__ __launch_bounds__(WAVE_SIZE * kDbSlices) void fa_dbias_reduce(
+    const float* __restrict__ part, float* __restrict__ dbias, int B,
+    int D) {
+  __shared__ float red[kDbSlices][WAVE_SIZE];
+  const int lane = threadIdx.x & 63;
+  const int slice = threadIdx.x / WAVE_SIZE;
+  const int c = blockIdx.x * WAVE_SIZE + lane;
+  float s = 0.f;
+  if (c < D) {
+    for (int p = slice; p < B; p += kDbSlices) s += part[(long)p * D + c];
+  }
+  red[slice][lane] = s;
+  __syncthreads();
+  if (slice == 0 && c < D) {
+    float t = 0.f;
+#pragma unroll
+    for (int p = 0; p < kDbSlices; ++p) t += red[p][lane];
+    dbias[c] = t;
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
 // Host wrappers
 // ---------------------------------------------------------------------------
+// Largest dynamic LDS request a launch on the current device accepts.
+static size_t fa_lds_limit_bytes() {
+  int dev = 0, limit = 0;
+  LV_CHECK_HIP(hipGetDevice(&dev));
+  LV_CHECK_HIP(hipDeviceGetAttribute(
+      &limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  return (size_t)limit;
+}
+
 static void check_btnh(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 4 &&
                   t.scalar_type() == torch::kBFloat16,
@@ -933,7 +1394,8 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
                                   int64_t left_chunks,
                                   c10::optional<torch::Tensor> dq_out,
                                   c10::optional<torch::Tensor> dk_out,
-                                  c10::optional<torch::Tensor> dv_out) {
+                                  c10::optional<torch::Tensor> dv_out,
+                                  const std::string& route) {
   // Every check comes before the first allocation or launch, so a
   // rejected call leaves caller-provided outputs untouched.
   const long sq = check_strided_btnh(q, "q");
@@ -967,12 +1429,132 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
                     dv_out->sizes() == k.sizes(),
                 "dq_out/dk_out/dv_out must have the shapes of q/k/v");
   }
+  const int nbias = 2 * (int)bias_clip + 1;
+  const bool bg = bias.has_value() && bias_grad;
+  // The fused kernel copies the head's whole bias row into LDS.
+  const bool bias_row_ok =
+      !bias.has_value() ||
+      (bias_clip >= 0 && bias->is_cuda() && bias->is_contiguous() &&
+       bias->scalar_type() == torch::kBFloat16 &&
+       bias->numel() == (long)N * nbias);
+
+  // Route, from shapes only (no device read, so the step still captures
+  // into a graph). 'fused' is the default fused configuration; the
+  // 'fused_*' names pick one configuration for A/B measurements.
+  enum { kTiles, kF10x2q64, kF8x3q64, kF10x2q32, kF8x3q32 } cfg = kTiles;
+  const bool want_fused = route.rfind("fused", 0) == 0;
+  TORCH_CHECK(route == "auto" || route == "tiles" || route == "fused" ||
+                  route == "fused_10x2_q64" || route == "fused_8x3_q64" ||
+                  route == "fused_10x2_q32" || route == "fused_8x3_q32",
+              "fa_bwd: unknown route '", route, "'");
+  size_t fused_lds = 0;
+  if (route != "tiles") {
+    int max_s;
+    if (route == "fused_8x3_q64") {
+      cfg = kF8x3q64;
+      max_s = fused_max_s<8, 3>();
+      fused_lds = fused_lds_bytes<64, 8, 3>(bias.has_value(), bg, nbias);
+    } else if (route == "fused_10x2_q64") {
+      cfg = kF10x2q64;
+      max_s = fused_max_s<10, 2>();
+      fused_lds = fused_lds_bytes<64, 10, 2>(bias.has_value(), bg, nbias);
+    } else if (route == "fused_10x2_q32") {
+      cfg = kF10x2q32;
+      max_s = fused_max_s<10, 2>();
+      fused_lds = fused_lds_bytes<32, 10, 2>(bias.has_value(), bg, nbias);
+    } else {
+      // Default: 8 waves x 3 strips, 32-row q-tiles. The only one of the
+      // four that keeps its accumulators out of scratch, and the fastest
+      // at the Conformer shape (docs/KERNEL_NOTES.md).
+      cfg = kF8x3q32;
+      max_s = fused_max_s<8, 3>();
+      fused_lds = fused_lds_bytes<32, 8, 3>(bias.has_value(), bg, nbias);
+    }
+    const char* why = nullptr;
+    if (H != 64) why = "H != 64";
+    else if (group != 1) why = "N != NKV";
+    else if (T != S) why = "T != S";
+    else if (S > max_s) why = "S above the route's limit";
+    else if (qseg.has_value() || kseg.has_value()) why = "segment ids";
+    else if (chunk_size > 0) why = "chunkwise mask";
+    else if (B > 65535) why = "B above the grid limit";
+    else if (!bias_row_ok) why = "bias is not bf16 [N, 2*bias_clip+1]";
+    else if (!lse.is_cuda() || !lse.is_contiguous() ||
+             lse.scalar_type() != torch::kFloat32 ||
+             lse.numel() != (long)B * N * T)
+      why = "lse is not fp32 [B,N,T]";
+    else if (fused_lds > fa_lds_limit_bytes()) why = "LDS request too large";
+    if (why) {
+      TORCH_CHECK(!want_fused, "fa_bwd: route '", route,
+                  "' does not support this call: ", why);
+      cfg = kTiles;
+    }
+  }
+
   auto stream = at::cuda::getCurrentCUDAStream();
+  const int* klp = klen.has_value() ? klen->data_ptr<int>() : nullptr;
+  const unsigned short* bp =
+      bias.has_value() ? (const unsigned short*)bias->data_ptr() : nullptr;
+
+  if (cfg != kTiles) {
+    torch::Tensor dq_t, dk_t, dv_t;
+    if (into) {
+      dq_t = *dq_out;
+      dk_t = *dk_out;
+      dv_t = *dv_out;
+    } else {
+      dq_t = torch::empty({B, T, N, H}, q.options());
+      dk_t = torch::empty({B, S, NKV, H}, q.options());
+      dv_t = torch::empty({B, S, NKV, H}, q.options());
+    }
+    auto fopts = q.options().dtype(torch::kFloat32);
+    // Without a bias gradient the table's gradient is all zeros, as on the
+    // tiles route.
+    torch::Tensor dbias_t =
+        bg ? torch::empty({N, nbias}, fopts)
+           : torch::zeros({bias.has_value() ? N : 0,
+                           bias.has_value() ? nbias : 0}, fopts);
+    torch::Tensor part;
+    if (bg) part = torch::empty({B, N, nbias}, fopts);
+    dim3 grid(N, B);
+#define FA_BWD_FUSED(BG, QTB, NWF, SPW)                                      \
+  hipLaunchKernelGGL(                                                        \
+      (fa_bwd_fused_kernel<64, BG, QTB, NWF, SPW>), grid,                    \
+      dim3(NWF * WAVE_SIZE), fused_lds, stream,                              \
+      (const unsigned short*)dout.data_ptr(),                                \
+      (const unsigned short*)q.data_ptr(),                                   \
+      (const unsigned short*)k.data_ptr(),                                   \
+      (const unsigned short*)v.data_ptr(),                                   \
+      (const unsigned short*)o.data_ptr(), lse.data_ptr<float>(), klp, bp,   \
+      (unsigned short*)dq_t.data_ptr(), (unsigned short*)dk_t.data_ptr(),    \
+      (unsigned short*)dv_t.data_ptr(),                                      \
+      bg ? part.data_ptr<float>() : nullptr, T, N, (int)win_l, (int)win_r,   \
+      (int)bias_clip, (float)scale, sq, sk, sv, sdq, sdk, sdv)
+    if (cfg == kF10x2q64) {
+      if (bg) FA_BWD_FUSED(true, 64, 10, 2); else FA_BWD_FUSED(false, 64, 10, 2);
+    } else if (cfg == kF8x3q64) {
+      if (bg) FA_BWD_FUSED(true, 64, 8, 3); else FA_BWD_FUSED(false, 64, 8, 3);
+    } else if (cfg == kF8x3q32) {
+      if (bg) FA_BWD_FUSED(true, 32, 8, 3); else FA_BWD_FUSED(false, 32, 8, 3);
+    } else {
+      if (bg) FA_BWD_FUSED(true, 32, 10, 2); else FA_BWD_FUSED(false, 32, 10, 2);
+    }
+#undef FA_BWD_FUSED
+    if (bg) {
+      const int D = N * nbias;
+      hipLaunchKernelGGL(fa_dbias_reduce, dim3(cdiv(D, WAVE_SIZE)),
+                         dim3(WAVE_SIZE * kDbSlices), 0, stream,
+                         part.data_ptr<float>(), dbias_t.data_ptr<float>(), B,
+                         D);
+    }
+    return {dq_t, dk_t, dv_t, dbias_t};
+  }
 
   auto delta = torch::empty({B, N, T}, q.options().dtype(torch::kFloat32));
   {
     long rows = (long)B * T * N;
-    dim3 grid((rows + NW - 1) / NW);
+    const int rpb = BLOCK / (H / 8);  // rows per block, H/8 lanes per row
+    dim3 grid((rows + rpb - 1) / rpb);
     if (H == 64)
       hipLaunchKernelGGL((fa_bwd_delta<64>), grid, dim3(BLOCK), 0, stream,
                          (const unsigned short*)dout.data_ptr(),
@@ -998,17 +1580,12 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
     dk_t = torch::zeros({B, S, NKV, H}, fopts);
     dv_t = torch::zeros({B, S, NKV, H}, fopts);
   }
-  const int nbias = 2 * (int)bias_clip + 1;
   torch::Tensor dbias_t = torch::zeros(
       {bias.has_value() ? N : 0, bias.has_value() ? nbias : 0},
       q.options().dtype(torch::kFloat32));
 
-  const int* klp = klen.has_value() ? klen->data_ptr<int>() : nullptr;
-  const unsigned short* bp =
-      bias.has_value() ? (const unsigned short*)bias->data_ptr() : nullptr;
   const int* qsp = qseg.has_value() ? qseg->data_ptr<int>() : nullptr;
   const int* ksp = kseg.has_value() ? kseg->data_ptr<int>() : nullptr;
-  bool bg = bias.has_value() && bias_grad;
 
   // Phase-skip bitmask for perf attribution only (results invalid when
   // nonzero): 1 = skip dQ math+atomics, 2 = skip transposed q/do
