@@ -515,9 +515,12 @@ def MatmulBias(x: torch.Tensor, w: torch.Tensor,
 # MatmulBiasDropoutAdd), the attention output padding rides in the
 # residual dropout kernel, and the residual gradient of a pre-LN block is
 # added inside the LayerNorm backward kernel (LayerNorm.FPropWithResidual).
-# Off: the unfused op sequence (split + copies + cat, addmm, dropout,
-# autograd's bias sum and gradient add), which the tests use as their
-# yardstick. Forward values are the same either way.
+# The LConv front (pw1 -> GLU -> padding -> depthwise conv) is one node
+# (MatmulBiasGluDwconv): the GLU and the mask run inside the tiled
+# convolution kernels, and d pw1_b comes from their column sums.
+# Off: the unfused op sequence (split + copies + cat, addmm, glu, mask
+# multiply, dropout, autograd's bias sum and gradient add), which the
+# tests use as their yardstick. Forward values are the same either way.
 def GlueFusion() -> bool:
   from lingvo_amd.ops import fusion
   return fusion.enabled()
@@ -569,6 +572,30 @@ def MatmulBiasDropoutAdd(x: torch.Tensor, w: torch.Tensor,
                                       paddings=paddings)
   return DeterministicDropoutAdd(MatmulBias(x, w, b), keep_prob, residual,
                                  op_seed, scale=scale, paddings=paddings)
+
+
+def MatmulBiasGluDwconv(x: torch.Tensor, pw1_w: torch.Tensor,
+                        pw1_b: torch.Tensor,
+                        paddings: Optional[torch.Tensor],
+                        dw_w: torch.Tensor, dw_b: Optional[torch.Tensor],
+                        causal: bool = False) -> torch.Tensor:
+  """depthwise_conv1d(ApplyPadding(paddings, glu(MatmulBias(x, pw1_w,
+  pw1_b))), dw_w, dw_b, causal): the front of the LConv module. With
+  GlueFusion on GPU bf16 it is one autograd node: the GLU output is never
+  written, and d pw1_b comes from the backward kernel's column sums."""
+  d = dw_w.shape[-1]
+  if (GlueFusion() and x.is_cuda and x.dim() == 3 and x.numel() > 0 and
+      d % 8 == 0 and pw1_b is not None and pw1_w.shape[-1] == 2 * d and
+      all(t is None or t.dtype == torch.bfloat16
+          for t in (x, pw1_w, pw1_b, dw_w, dw_b))):
+    from lingvo_amd.ops import conv1d as conv1d_ops
+    return conv1d_ops.linear_glu_dwconv(x, pw1_w, pw1_b, paddings, dw_w,
+                                        dw_b, causal=causal)
+  from lingvo_amd.ops import conv1d as conv1d_ops
+  h = torch.nn.functional.glu(MatmulBias(x, pw1_w, pw1_b), dim=-1)
+  if paddings is not None:
+    h = ApplyPadding(paddings, h)
+  return conv1d_ops.depthwise_conv1d(h, dw_w, dw_b, causal=causal)
 
 
 class Timer:

@@ -70,12 +70,11 @@ class LConvLayer(BaseLayer):
             paddings: Optional[torch.Tensor] = None) -> torch.Tensor:
     p = self.p
     x, residual = transformer_lib.PreLn(self.ln, theta.ln, inputs)
-    x = py_utils.MatmulBias(x, theta.pw1_w, theta.pw1_b)
-    x = F.glu(x, dim=-1)  # fused GLU (single kernel fwd + bwd)
-    if paddings is not None:
-      x = py_utils.ApplyPadding(paddings, x)
-    x = conv1d_ops.depthwise_conv1d(x, theta.dw_w, theta.dw_b,
-                                    causal=p.is_causal)
+    # pw1 -> GLU -> padding -> depthwise conv; one autograd node whose
+    # kernels apply the GLU and the mask while staging (GlueFusion).
+    x = py_utils.MatmulBiasGluDwconv(x, theta.pw1_w, theta.pw1_b, paddings,
+                                     theta.dw_w, theta.dw_b,
+                                     causal=p.is_causal)
     if p.conv_norm == 'layer':
       x = self.norm.FProp(theta.norm, x)
       if paddings is not None:

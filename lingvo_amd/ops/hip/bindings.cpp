@@ -46,9 +46,28 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
 
 // conv1d.hip
 torch::Tensor dwconv1d_fwd(torch::Tensor x, torch::Tensor w,
-                           c10::optional<torch::Tensor> bias, int64_t pad);
-std::vector<torch::Tensor> dwconv1d_bwd(torch::Tensor dy, torch::Tensor x,
-                                        torch::Tensor w, int64_t pad);
+                           c10::optional<torch::Tensor> bias, int64_t pad,
+                           const std::string& route,
+                           c10::optional<torch::Tensor> y_out);
+std::vector<torch::Tensor> dwconv1d_bwd(
+    torch::Tensor dy, torch::Tensor x, torch::Tensor w, int64_t pad,
+    const std::string& route, c10::optional<torch::Tensor> dx_out,
+    c10::optional<torch::Tensor> dw_out, c10::optional<torch::Tensor> db_out);
+torch::Tensor glu_dwconv1d_fwd(torch::Tensor h,
+                               c10::optional<torch::Tensor> paddings,
+                               torch::Tensor w,
+                               c10::optional<torch::Tensor> bias, int64_t pad,
+                               const std::string& route,
+                               c10::optional<torch::Tensor> y_out);
+std::vector<torch::Tensor> glu_dwconv1d_bwd(
+    torch::Tensor dy, torch::Tensor h, c10::optional<torch::Tensor> paddings,
+    torch::Tensor w, int64_t pad, const std::string& route,
+    c10::optional<torch::Tensor> dh_out, c10::optional<torch::Tensor> dw_out,
+    c10::optional<torch::Tensor> db_out,
+    c10::optional<torch::Tensor> dcol_out);
+
+// dwconv_tiled.hip
+int64_t dwconv_tile_len();
 
 // softmax_xent.hip
 std::vector<torch::Tensor> xent_fwd(torch::Tensor logits,
@@ -78,7 +97,8 @@ std::vector<torch::Tensor> group_norm_fwd(torch::Tensor x,
                                           torch::Tensor beta,
                                           c10::optional<torch::Tensor> pad,
                                           int64_t groups, double eps,
-                                          int64_t act);
+                                          int64_t act,
+                                          const std::string& route);
 std::vector<torch::Tensor> group_norm_bwd(torch::Tensor dy, torch::Tensor x,
                                           torch::Tensor gamma,
                                           torch::Tensor beta,
@@ -183,7 +203,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   RegisterInputPipeline(m);
   RegisterWpmTokenizer(m);
   RegisterRecordBatcher(m);
-  m.def("group_norm_fwd", &group_norm_fwd, "Fused padded GroupNorm fwd");
+  m.def("group_norm_fwd", &group_norm_fwd, "Fused padded GroupNorm fwd",
+        py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("pad"),
+        py::arg("groups"), py::arg("eps"), py::arg("act"),
+        py::arg("route") = "auto");
   m.def("group_norm_bwd", &group_norm_bwd, "Fused padded GroupNorm bwd");
   m.def("lstm_gates_fwd", &lstm_gates_fwd_op, "Fused LSTM gates fwd");
   m.def("lstm_gates_bwd", &lstm_gates_bwd_op, "Fused LSTM gates bwd");
@@ -193,8 +216,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused dropout bwd + fp32 column sums of dx");
   m.def("xent_fwd", &xent_fwd, "Fused softmax-xent fwd");
   m.def("xent_bwd", &xent_bwd, "Fused softmax-xent bwd");
-  m.def("dwconv1d_fwd", &dwconv1d_fwd, "Depthwise time conv fwd");
-  m.def("dwconv1d_bwd", &dwconv1d_bwd, "Depthwise time conv bwd");
+  m.def("dwconv1d_fwd", &dwconv1d_fwd, "Depthwise time conv fwd",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("pad"),
+        py::arg("route") = "auto", py::arg("y_out") = py::none());
+  m.def("dwconv1d_bwd", &dwconv1d_bwd, "Depthwise time conv bwd",
+        py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("pad"),
+        py::arg("route") = "auto", py::arg("dx_out") = py::none(),
+        py::arg("dw_out") = py::none(), py::arg("db_out") = py::none());
+  m.def("glu_dwconv1d_fwd", &glu_dwconv1d_fwd,
+        "conv(mask * glu(h)) + bias in one kernel", py::arg("h"),
+        py::arg("paddings"), py::arg("w"), py::arg("bias"), py::arg("pad"),
+        py::arg("route") = "auto", py::arg("y_out") = py::none());
+  m.def("glu_dwconv1d_bwd", &glu_dwconv1d_bwd,
+        "dh, dw, db and the fp32 column sums of dh of glu_dwconv1d_fwd",
+        py::arg("dy"), py::arg("h"), py::arg("paddings"), py::arg("w"),
+        py::arg("pad"), py::arg("route") = "auto",
+        py::arg("dh_out") = py::none(), py::arg("dw_out") = py::none(),
+        py::arg("db_out") = py::none(), py::arg("dcol_out") = py::none());
+  m.def("dwconv_tile_len", &dwconv_tile_len,
+        "Time rows per tile of the tiled depthwise convolution");
   m.def("layer_norm_fwd", &layer_norm_fwd, "Fused LayerNorm/RMSNorm fwd");
   m.def("layer_norm_bwd", &layer_norm_bwd, "Fused LayerNorm/RMSNorm bwd",
         py::arg("dy"), py::arg("x"), py::arg("scale"), py::arg("mean"),

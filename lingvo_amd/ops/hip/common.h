@@ -89,3 +89,8 @@ static inline int memory_bound_grid(long total_work, int block_size,
   long want = (total_work + block_size - 1) / block_size;
   return (int)(want < cap_blocks ? (want > 0 ? want : 1) : cap_blocks);
 }
+
+// partials [nslab, D] fp32 -> out [D], slabs summed in a fixed order
+// (colsum_reduce_kernel, dropout.hip).
+void colsum_reduce(const float* partials, float* out, int nslab, long D,
+                   hipStream_t stream);

@@ -9,13 +9,22 @@
 // Inputs are pre-masked by paddings on the Python side; outputs are
 // re-masked there too.
 //
-// Memory-bound: vectorized ushort8 IO, one thread per 8 channels of one
-// (b, t) row, grid-stride; taps hit L1/L2 (row re-use across t).
+// Two routes. 'tiled' (dwconv_tiled.hip, the default) stages a time tile
+// in LDS and slides a register window over it; it also has the fused
+// GLU + padding front of the Conformer LConv (glu_dwconv1d_*). 'naive',
+// below, is the yardstick: vectorized ushort8 IO, one thread per 8 channels
+// of one (b, t) row, grid-stride; taps hit L1/L2 (row re-use across t).
+// Each route has its own weight-gradient kernel; both write per-group
+// fp32 partials that dwconv_bwd_dw_reduce sums in order.
 
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 
+#include <array>
+#include <string>
+
 #include "common.h"
+#include "dwconv_tiled.h"
 
 namespace {
 
@@ -76,90 +85,6 @@ __global__ void dwconv_fwd(const unsigned short* __restrict__ x,
 #pragma unroll
     for (int e = 0; e < 8; ++e) ov[e] = float_to_bf16_bits(acc[e]);
     *reinterpret_cast<ushortx8*>(y + (b * T + t) * D + dv * 8) = ov;
-  }
-}
-
-// Register-window fwd variant (A/B, default OFF — measured SLOWER:
-// 0.77 vs 0.44 ms at the bench shape): thread computes R consecutive
-// t rows of one 8-channel vec with taps in registers and a shifting x
-// window, cutting x re-reads from KT to (KT+R-1)/R per output. The
-// loss shows the plain kernel is NOT L1-bound; the ~128-VGPR tap
-// array costs more occupancy than the traffic saving returns. Kept
-// behind LINGVO_DWCONV_REG=1 as measured methodology.
-template <int KT, int R>
-__global__ __launch_bounds__(256) void dwconv_fwd_reg(
-    const unsigned short* __restrict__ x,
-    const unsigned short* __restrict__ w,
-    const unsigned short* __restrict__ bias,
-    unsigned short* __restrict__ y, int B, int T, int D, int pad) {
-  const int dvec = D / 8;
-  const int tblks = (T + R - 1) / R;
-  const long nwork = (long)B * tblks * dvec;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nwork;
-       i += (long)gridDim.x * blockDim.x) {
-    const int dv = (int)(i % dvec);
-    const long bt = i / dvec;
-    const int t0 = (int)(bt % tblks) * R;
-    const long b = bt / tblks;
-    // Tap registers for this channel octet.
-    ushortx8 wv[KT];
-#pragma unroll
-    for (int j = 0; j < KT; ++j) {
-      wv[j] = *reinterpret_cast<const ushortx8*>(w + j * D + dv * 8);
-    }
-    float acc[R][8];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (bias) {
-        ushortx8 bv = *reinterpret_cast<const ushortx8*>(bias + dv * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[r][e] = bf16_bits_to_float(bv[e]);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[r][e] = 0.f;
-      }
-    }
-    const long rowbase = b * T;
-    auto loadx = [&](int t) -> ushortx8 {
-      ushortx8 v;
-      if (t >= 0 && t < T) {
-        v = *reinterpret_cast<const ushortx8*>(
-            x + (rowbase + t) * D + dv * 8);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0;
-      }
-      return v;
-    };
-    // Window W[r] = x[t0 + r + j - pad] for the current tap j.
-    ushortx8 W[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) W[r] = loadx(t0 + r - pad);
-#pragma unroll
-    for (int j = 0; j < KT; ++j) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          acc[r][e] += bf16_bits_to_float(W[r][e]) *
-                       bf16_bits_to_float(wv[j][e]);
-        }
-      }
-      if (j + 1 < KT) {
-#pragma unroll
-        for (int r = 0; r + 1 < R; ++r) W[r] = W[r + 1];
-        W[R - 1] = loadx(t0 + (R - 1) + (j + 1) - pad);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int t = t0 + r;
-      if (t >= T) continue;
-      ushortx8 ov;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) ov[e] = float_to_bf16_bits(acc[r][e]);
-      *reinterpret_cast<ushortx8*>(y + (rowbase + t) * D + dv * 8) = ov;
-    }
   }
 }
 
@@ -374,80 +299,239 @@ __global__ void dwconv_bwd_dw_reduce(const float* __restrict__ dw_part,
 
 }  // namespace
 
-torch::Tensor dwconv1d_fwd(torch::Tensor x, torch::Tensor w,
-                           c10::optional<torch::Tensor> bias, int64_t pad) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 3 &&
-              x.scalar_type() == torch::kBFloat16, "x must be bf16 [B,T,D]");
-  TORCH_CHECK(x.size(2) % 8 == 0, "D must be divisible by 8");
-  const int B = x.size(0), T = x.size(1), D = x.size(2), K = w.size(0);
-  TORCH_CHECK(K < MAXK, "kernel size < ", MAXK);
-  auto y = torch::empty_like(x);
-  auto stream = at::cuda::getCurrentCUDAStream();
-  long nvec = (long)B * T * (D / 8);
-  int grid = memory_bound_grid(nvec, 256);
-  // Measured: full K unroll (KT=32) raises register pressure and costs
-  // ~50% (8.2 -> 12.5 ms/step at the bench shape). Runtime-K path wins
-  // for the naive form; LINGVO_DWCONV_REG=1 selects the register-window
-  // variant (A/B knob).
-  static const bool use_reg = []() {
-    const char* e = getenv("LINGVO_DWCONV_REG");
-    return e && e[0] == '1';
-  }();
-  if (use_reg && K == 32) {
-    long nwork = (long)B * ((T + 3) / 4) * (D / 8);
-    hipLaunchKernelGGL((dwconv_fwd_reg<32, 4>),
-                       dim3(memory_bound_grid(nwork, 256)), dim3(256), 0,
-                       stream, (const unsigned short*)x.data_ptr(),
-                       (const unsigned short*)w.data_ptr(),
-                       bias.has_value() ? (const unsigned short*)
-                                              bias->data_ptr()
-                                        : nullptr,
-                       (unsigned short*)y.data_ptr(), B, T, D, (int)pad);
-    return y;
-  }
-  auto fwd_kern = dwconv_fwd<0>;
-  hipLaunchKernelGGL(fwd_kern, dim3(grid), dim3(256), 0, stream,
-                     (const unsigned short*)x.data_ptr(),
-                     (const unsigned short*)w.data_ptr(),
-                     bias.has_value() ? (const unsigned short*)
-                                            bias->data_ptr()
-                                      : nullptr,
-                     (unsigned short*)y.data_ptr(), B, T, D, K, (int)pad);
-  return y;
+namespace {
+
+const unsigned short* bf16_ptr(const torch::Tensor& t) {
+  return (const unsigned short*)t.data_ptr();
 }
 
-std::vector<torch::Tensor> dwconv1d_bwd(torch::Tensor dy, torch::Tensor x,
-                                        torch::Tensor w, int64_t pad) {
-  const int B = x.size(0), T = x.size(1), D = x.size(2), K = w.size(0);
-  auto dx = torch::empty_like(x);
-  auto opts = x.options().dtype(torch::kFloat32);
-  auto dw = torch::zeros({K, D}, opts);
-  auto db = torch::zeros({D}, opts);
-  auto stream = at::cuda::getCurrentCUDAStream();
-  long nvec = (long)B * T * (D / 8);
-  auto dx_kern = dwconv_bwd_dx<0>;
-  hipLaunchKernelGGL(dx_kern, dim3(memory_bound_grid(nvec, 256)),
-                     dim3(256), 0, stream,
-                     (const unsigned short*)dy.data_ptr(),
-                     (const unsigned short*)w.data_ptr(),
-                     (unsigned short*)dx.data_ptr(), B, T, D, K, (int)pad);
+const unsigned short* opt_ptr(const c10::optional<torch::Tensor>& t) {
+  return t.has_value() ? bf16_ptr(*t) : nullptr;
+}
+
+bool is_bf16_cuda(const torch::Tensor& t) {
+  return t.is_cuda() && t.is_contiguous() &&
+         t.scalar_type() == torch::kBFloat16;
+}
+
+// 'auto' | 'naive' | 'tiled'. True for the tiled kernels, false for the
+// per-thread tap loop.
+bool pick_tiled(const std::string& route, int64_t B, int64_t T, int64_t D,
+                int64_t K) {
+  if (route == "naive") return false;
+  const bool ok = dwconv_tiled_supported(B, T, D, K);
+  if (route == "auto") return ok;
+  TORCH_CHECK(route == "tiled",
+              "route must be 'auto', 'naive' or 'tiled', got '", route, "'");
+  TORCH_CHECK(ok, "route='tiled' does not support B=", B, " T=", T, " D=", D,
+              " K=", K);
+  return true;
+}
+
+// A caller-provided output, or a fresh one.
+torch::Tensor out_or_empty(const c10::optional<torch::Tensor>& out,
+                           at::IntArrayRef sizes,
+                           const torch::TensorOptions& opts,
+                           const char* name) {
+  if (!out.has_value()) return torch::empty(sizes, opts);
+  TORCH_CHECK(out->is_cuda() && out->is_contiguous() &&
+              out->scalar_type() == opts.dtype().toScalarType() &&
+              out->sizes() == sizes &&
+              reinterpret_cast<uintptr_t>(out->data_ptr()) % 16 == 0,
+              name, " must be a contiguous 16-byte aligned tensor of shape ",
+              sizes);
+  return *out;
+}
+
+void check_conv_args(const torch::Tensor& x, const torch::Tensor& w,
+                     const c10::optional<torch::Tensor>& bias, int64_t D,
+                     int64_t pad) {
+  TORCH_CHECK(D % 8 == 0, "D must be divisible by 8");
+  TORCH_CHECK(is_bf16_cuda(w) && w.dim() == 2 && w.size(1) == D,
+              "w must be contiguous bf16 [K,D]");
+  const int64_t K = w.size(0);
+  TORCH_CHECK(K >= 1 && K < MAXK, "kernel size < ", MAXK);
+  TORCH_CHECK(pad >= 0 && pad < K, "pad must be in [0, K)");
+  TORCH_CHECK(!bias.has_value() ||
+              (is_bf16_cuda(*bias) && bias->dim() == 1 && bias->size(0) == D),
+              "bias must be contiguous bf16 [D]");
+}
+
+// dw/db of conv(u, w) from dy and u; the tiled kernel also takes h in
+// place of u and recomputes the GLU (glu, padm).
+void launch_bwd_dw(bool tiled, bool glu, const torch::Tensor& dy,
+                   const torch::Tensor& x, const unsigned short* padm,
+                   torch::Tensor& dw, torch::Tensor& db, int B, int T, int D,
+                   int K, int pad, hipStream_t stream) {
+  TORCH_CHECK(tiled || !glu, "the naive weight gradient takes u, not h");
+  auto opts = dw.options();
   long nchunks = ((long)B * T + DW_CHUNK - 1) / DW_CHUNK;
   int dblks = (D + DW_DBLK - 1) / DW_DBLK;
-  int ngroups = (int)std::min<long>(std::max<long>(1, 1024 / dblks),
-                                    nchunks);
+  int ngroups = tiled ? (int)dwconv_tiled_dw_groups(B, T, D)
+                      : (int)std::min<long>(
+                            std::max<long>(1, 1024 / dblks), nchunks);
   auto dw_part = torch::empty({(long)ngroups * K * D}, opts);
   auto db_part = torch::empty({(long)ngroups * D}, opts);
-  dim3 grid_w(dblks, ngroups);
-  hipLaunchKernelGGL(dwconv_bwd_dw, grid_w, dim3(256), 0, stream,
-                     (const unsigned short*)dy.data_ptr(),
-                     (const unsigned short*)x.data_ptr(),
-                     dw_part.data_ptr<float>(), db_part.data_ptr<float>(),
-                     B, T, D, K, (int)pad, ngroups);
+  if (tiled) {
+    dwconv_tiled_dw(glu, bf16_ptr(dy), bf16_ptr(x), padm,
+                    dw_part.data_ptr<float>(), db_part.data_ptr<float>(), B,
+                    T, D, K, pad, ngroups, stream);
+  } else {
+    dim3 grid_w(dblks, ngroups);
+    hipLaunchKernelGGL(dwconv_bwd_dw, grid_w, dim3(256), 0, stream,
+                       bf16_ptr(dy), bf16_ptr(x), dw_part.data_ptr<float>(),
+                       db_part.data_ptr<float>(), B, T, D, K, pad, ngroups);
+  }
   const long kd = (long)K * D;
   hipLaunchKernelGGL(dwconv_bwd_dw_reduce,
                      dim3((int)std::min<long>((kd + D + 255) / 256, 1024)),
                      dim3(256), 0, stream, dw_part.data_ptr<float>(),
                      db_part.data_ptr<float>(), dw.data_ptr<float>(),
                      db.data_ptr<float>(), kd, D, ngroups);
+}
+
+}  // namespace
+
+torch::Tensor dwconv1d_fwd(torch::Tensor x, torch::Tensor w,
+                           c10::optional<torch::Tensor> bias, int64_t pad,
+                           const std::string& route,
+                           c10::optional<torch::Tensor> y_out) {
+  TORCH_CHECK(is_bf16_cuda(x) && x.dim() == 3, "x must be bf16 [B,T,D]");
+  const int B = x.size(0), T = x.size(1), D = x.size(2);
+  check_conv_args(x, w, bias, D, pad);
+  const int K = w.size(0);
+  if (x.numel() == 0) return out_or_empty(y_out, x.sizes(), x.options(), "y_out");
+  const bool tiled = pick_tiled(route, B, T, D, K);
+  auto y = out_or_empty(y_out, x.sizes(), x.options(), "y_out");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (tiled) {
+    dwconv_tiled_fwd(bf16_ptr(x), bf16_ptr(w), opt_ptr(bias),
+                     (unsigned short*)y.data_ptr(), B, T, D, K, (int)pad,
+                     stream);
+    return y;
+  }
+  // Measured: full K unroll (KT=32) of the per-thread loop raises register
+  // pressure and costs ~50% (8.2 -> 12.5 ms/step at the bench shape), so
+  // the naive route keeps the runtime-K form.
+  long nvec = (long)B * T * (D / 8);
+  auto fwd_kern = dwconv_fwd<0>;
+  hipLaunchKernelGGL(fwd_kern, dim3(memory_bound_grid(nvec, 256)), dim3(256),
+                     0, stream, bf16_ptr(x), bf16_ptr(w), opt_ptr(bias),
+                     (unsigned short*)y.data_ptr(), B, T, D, K, (int)pad);
+  return y;
+}
+
+std::vector<torch::Tensor> dwconv1d_bwd(
+    torch::Tensor dy, torch::Tensor x, torch::Tensor w, int64_t pad,
+    const std::string& route, c10::optional<torch::Tensor> dx_out,
+    c10::optional<torch::Tensor> dw_out,
+    c10::optional<torch::Tensor> db_out) {
+  TORCH_CHECK(is_bf16_cuda(x) && x.dim() == 3, "x must be bf16 [B,T,D]");
+  TORCH_CHECK(is_bf16_cuda(dy) && dy.sizes() == x.sizes(),
+              "dy must be contiguous bf16 shaped like x");
+  const int B = x.size(0), T = x.size(1), D = x.size(2);
+  check_conv_args(x, w, c10::nullopt, D, pad);
+  const int K = w.size(0);
+  auto opts = x.options().dtype(torch::kFloat32);
+  if (x.numel() == 0) {
+    // Nothing to sum: empty dx, zero dw and db.
+    auto dx = out_or_empty(dx_out, x.sizes(), x.options(), "dx_out");
+    auto dw = out_or_empty(dw_out, {K, D}, opts, "dw_out");
+    auto db = out_or_empty(db_out, {D}, opts, "db_out");
+    return {dx, dw.zero_(), db.zero_()};
+  }
+  const bool tiled = pick_tiled(route, B, T, D, K);
+  auto dx = out_or_empty(dx_out, x.sizes(), x.options(), "dx_out");
+  auto dw = out_or_empty(dw_out, {K, D}, opts, "dw_out");
+  auto db = out_or_empty(db_out, {D}, opts, "db_out");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (tiled) {
+    dwconv_tiled_dx(bf16_ptr(dy), bf16_ptr(w), (unsigned short*)dx.data_ptr(),
+                    B, T, D, K, (int)pad, stream);
+  } else {
+    long nvec = (long)B * T * (D / 8);
+    auto dx_kern = dwconv_bwd_dx<0>;
+    hipLaunchKernelGGL(dx_kern, dim3(memory_bound_grid(nvec, 256)), dim3(256),
+                       0, stream, bf16_ptr(dy), bf16_ptr(w),
+                       (unsigned short*)dx.data_ptr(), B, T, D, K, (int)pad);
+  }
+  launch_bwd_dw(tiled, false, dy, x, nullptr, dw, db, B, T, D, K, (int)pad,
+                stream);
   return {dx, dw, db};
+}
+
+namespace {
+
+// Shared argument checks of the fused GLU front; returns {B, T, D, K}.
+std::array<int, 4> check_glu_args(const torch::Tensor& h,
+                                  const c10::optional<torch::Tensor>& paddings,
+                                  const torch::Tensor& w,
+                                  const c10::optional<torch::Tensor>& bias,
+                                  int64_t pad) {
+  TORCH_CHECK(h.is_cuda() && h.dim() == 3 &&
+              h.scalar_type() == torch::kBFloat16, "h must be bf16 [B,T,2D]");
+  TORCH_CHECK(h.is_contiguous(), "h must be contiguous");
+  TORCH_CHECK(w.dim() == 2 && h.size(2) == 2 * w.size(1),
+              "h.shape[-1] must be 2*D with w [K,D]");
+  const int64_t D = w.size(1);
+  check_conv_args(h, w, bias, D, pad);
+  TORCH_CHECK(h.numel() > 0, "empty input");
+  TORCH_CHECK(!paddings.has_value() ||
+              (is_bf16_cuda(*paddings) && paddings->dim() == 2 &&
+               paddings->size(0) == h.size(0) &&
+               paddings->size(1) == h.size(1)),
+              "paddings must be contiguous bf16 [B,T]");
+  return {(int)h.size(0), (int)h.size(1), (int)D, (int)w.size(0)};
+}
+
+}  // namespace
+
+// y = conv(mask * glu(h), w) + bias without writing glu(h) to memory.
+torch::Tensor glu_dwconv1d_fwd(torch::Tensor h,
+                               c10::optional<torch::Tensor> paddings,
+                               torch::Tensor w,
+                               c10::optional<torch::Tensor> bias, int64_t pad,
+                               const std::string& route,
+                               c10::optional<torch::Tensor> y_out) {
+  const auto s = check_glu_args(h, paddings, w, bias, pad);
+  const int B = s[0], T = s[1], D = s[2], K = s[3];
+  TORCH_CHECK(route != "naive", "the fused front has no naive route");
+  pick_tiled(route == "auto" ? "tiled" : route, B, T, D, K);
+  auto y = out_or_empty(y_out, {B, T, D}, h.options(), "y_out");
+  glu_dwconv_tiled_fwd(bf16_ptr(h), opt_ptr(paddings), bf16_ptr(w),
+                       opt_ptr(bias), (unsigned short*)y.data_ptr(), B, T, D,
+                       K, (int)pad, at::cuda::getCurrentCUDAStream());
+  return y;
+}
+
+// Returns {dh [B,T,2D] bf16, dw [K,D], db [D], colsum(dh) [2D]} (fp32).
+std::vector<torch::Tensor> glu_dwconv1d_bwd(
+    torch::Tensor dy, torch::Tensor h, c10::optional<torch::Tensor> paddings,
+    torch::Tensor w, int64_t pad, const std::string& route,
+    c10::optional<torch::Tensor> dh_out, c10::optional<torch::Tensor> dw_out,
+    c10::optional<torch::Tensor> db_out,
+    c10::optional<torch::Tensor> dcol_out) {
+  const auto s = check_glu_args(h, paddings, w, c10::nullopt, pad);
+  const int B = s[0], T = s[1], D = s[2], K = s[3];
+  TORCH_CHECK(is_bf16_cuda(dy) && dy.dim() == 3 && dy.size(0) == B &&
+              dy.size(1) == T && dy.size(2) == D,
+              "dy must be contiguous bf16 [B,T,D]");
+  TORCH_CHECK(route != "naive", "the fused front has no naive route");
+  pick_tiled(route == "auto" ? "tiled" : route, B, T, D, K);
+  auto opts = h.options().dtype(torch::kFloat32);
+  auto dh = out_or_empty(dh_out, {B, T, 2 * D}, h.options(), "dh_out");
+  auto dw = out_or_empty(dw_out, {K, D}, opts, "dw_out");
+  auto db = out_or_empty(db_out, {D}, opts, "db_out");
+  auto dcol = out_or_empty(dcol_out, {2 * D}, opts, "dcol_out");
+  const int groups = (int)dwconv_tiled_groups(B, T);
+  auto cs_part = torch::empty({groups, 2 * D}, opts);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  glu_dwconv_tiled_dx(bf16_ptr(dy), bf16_ptr(h), opt_ptr(paddings),
+                      bf16_ptr(w), (unsigned short*)dh.data_ptr(),
+                      cs_part.data_ptr<float>(), B, T, D, K, (int)pad, stream);
+  colsum_reduce(cs_part.data_ptr<float>(), dcol.data_ptr<float>(), groups,
+                2L * D, stream);
+  launch_bwd_dw(true, true, dy, h, opt_ptr(paddings), dw, db, B, T, D, K,
+                (int)pad, stream);
+  return {dh, dw, db, dcol};
 }

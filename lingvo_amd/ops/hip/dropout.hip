@@ -215,6 +215,12 @@ void colsum_reduce_kernel(const float* __restrict__ partials,
 
 }  // namespace
 
+void colsum_reduce(const float* partials, float* out, int nslab, long D,
+                   hipStream_t stream) {
+  hipLaunchKernelGGL(colsum_reduce_kernel, dim3(cdiv(D, 16)), dim3(256), 0,
+                     stream, partials, out, nslab, D);
+}
+
 torch::Tensor dropout_fwd(torch::Tensor x, c10::optional<torch::Tensor> res,
                           int64_t seed, c10::optional<torch::Tensor> step_seed,
                           double keep, int64_t act, double scale,
@@ -348,8 +354,7 @@ std::vector<torch::Tensor> dropout_bwd_colsum(
     LAUNCH_BWD_CS(0);
   }
 #undef LAUNCH_BWD_CS
-  hipLaunchKernelGGL(colsum_reduce_kernel, dim3(cdiv(d, 16)), dim3(256), 0,
-                     stream, partials.data_ptr<float>(),
-                     colsum.data_ptr<float>(), gy, (long)d);
+  colsum_reduce(partials.data_ptr<float>(), colsum.data_ptr<float>(), gy,
+                (long)d, stream);
   return {dx, colsum};
 }

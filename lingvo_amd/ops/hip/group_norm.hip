@@ -12,6 +12,8 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 
+#include <string>
+
 #include "common.h"
 
 namespace {
@@ -70,6 +72,86 @@ __global__ __launch_bounds__(GN_BLOCK) void gn_fwd_kernel(
     if (act == 1) out = out / (1.f + __expf(-out));  // fused SiLU
     out *= (1.f - pad);
     y[((long)b * T + t) * D + c] = float_to_bf16_bits(out);
+  }
+}
+
+// Vectorized fwd for cg % 8 == 0, laid out like gn_bwd_vec_kernel: each
+// thread owns one 8-channel octet and strides over rows, so all traffic
+// is ushortx8, the padding is read once per row and there is no divide
+// or modulo per element. Moments stay fp32; they differ from the scalar
+// kernel only through summation order.
+__global__ __launch_bounds__(GN_BLOCK) void gn_fwd_vec_kernel(
+    const unsigned short* __restrict__ x,
+    const unsigned short* __restrict__ gamma,
+    const unsigned short* __restrict__ beta,
+    const unsigned short* __restrict__ paddings,  // [B,T] bf16 or null
+    unsigned short* __restrict__ y, float* __restrict__ mean_out,
+    float* __restrict__ rstd_out, int B, int T, int D, int G, float eps,
+    int act) {
+  __shared__ float scratch[GN_WAVES];
+  const int b = blockIdx.x / G;
+  const int g = blockIdx.x % G;
+  const int cg = D / G;
+  const int noct = cg / 8;
+  const int tid = threadIdx.x;
+  const int oct = tid % noct;
+  const int rt = tid / noct;
+  const int rstep = GN_BLOCK / noct;
+  // Threads past the last whole row lane idle (noct need not divide 256).
+  const int t_first = rt < rstep ? rt : T;
+  const long col0 = (long)g * cg + (rt < rstep ? oct : 0) * 8;
+
+  float sum = 0.f, sumsq = 0.f, count = 0.f;
+  for (int t = t_first; t < T; t += rstep) {
+    const float pad =
+        paddings ? bf16_bits_to_float(paddings[(long)b * T + t]) : 0.f;
+    if (pad >= 0.5f) continue;
+    const ushortx8 xv = *reinterpret_cast<const ushortx8*>(
+        x + ((long)b * T + t) * D + col0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float v = bf16_bits_to_float(xv[e]);
+      sum += v;
+      sumsq += v * v;
+    }
+    count += 8.f;
+  }
+  sum = block_reduce_sum<GN_WAVES>(sum, scratch);
+  sumsq = block_reduce_sum<GN_WAVES>(sumsq, scratch);
+  count = block_reduce_sum<GN_WAVES>(count, scratch);
+  count = fmaxf(count, 1.f);
+  const float mu = sum / count;
+  const float var = sumsq / count - mu * mu;
+  const float rstd = rsqrtf(var + eps);
+  if (tid == 0) {
+    mean_out[(long)b * G + g] = mu;
+    rstd_out[(long)b * G + g] = rstd;
+  }
+
+  float w[8], bb[8];
+  {
+    const ushortx8 gv = *reinterpret_cast<const ushortx8*>(gamma + col0);
+    const ushortx8 bv = *reinterpret_cast<const ushortx8*>(beta + col0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      w[e] = 1.f + bf16_bits_to_float(gv[e]);
+      bb[e] = bf16_bits_to_float(bv[e]);
+    }
+  }
+  for (int t = t_first; t < T; t += rstep) {
+    const float pad =
+        paddings ? bf16_bits_to_float(paddings[(long)b * T + t]) : 0.f;
+    const long base = ((long)b * T + t) * D + col0;
+    const ushortx8 xv = *reinterpret_cast<const ushortx8*>(x + base);
+    ushortx8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float out = (bf16_bits_to_float(xv[e]) - mu) * rstd * w[e] + bb[e];
+      if (act == 1) out = out / (1.f + __expf(-out));  // fused SiLU
+      out *= (1.f - pad);
+      o[e] = float_to_bf16_bits(out);
+    }
+    *reinterpret_cast<ushortx8*>(y + base) = o;
   }
 }
 
@@ -275,12 +357,20 @@ std::vector<torch::Tensor> group_norm_fwd(torch::Tensor x,
                                           torch::Tensor beta,
                                           c10::optional<torch::Tensor> pad,
                                           int64_t groups, double eps,
-                                          int64_t act) {
+                                          int64_t act,
+                                          const std::string& route) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 3 &&
               x.scalar_type() == torch::kBFloat16);
   const int B = x.size(0), T = x.size(1), D = x.size(2);
   const int G = (int)groups;
   TORCH_CHECK(D % G == 0 && D / G <= 64, "cg must be <= 64");
+  // 'auto' takes the vector kernel for cg % 8 == 0; 'scalar' forces the
+  // per-element kernel (the tests' yardstick).
+  TORCH_CHECK(route == "auto" || route == "scalar" || route == "vec",
+              "route must be 'auto', 'scalar' or 'vec'");
+  const bool can_vec = (D / G) % 8 == 0;
+  TORCH_CHECK(route != "vec" || can_vec, "route='vec' needs cg % 8 == 0");
+  const bool vec = can_vec && route != "scalar";
   auto y = torch::empty_like(x);
   auto opts = x.options().dtype(torch::kFloat32);
   auto mean = torch::empty({(long)B * G}, opts);
@@ -288,7 +378,8 @@ std::vector<torch::Tensor> group_norm_fwd(torch::Tensor x,
   auto stream = at::cuda::getCurrentCUDAStream();
   TORCH_CHECK(act == 0 || (D / G) % 8 == 0,
               "fused activation needs cg % 8 == 0");
-  hipLaunchKernelGGL(gn_fwd_kernel, dim3(B * G), dim3(GN_BLOCK), 0, stream,
+  hipLaunchKernelGGL(vec ? gn_fwd_vec_kernel : gn_fwd_kernel, dim3(B * G),
+                     dim3(GN_BLOCK), 0, stream,
                      (const unsigned short*)x.data_ptr(),
                      (const unsigned short*)gamma.data_ptr(),
                      (const unsigned short*)beta.data_ptr(),
