@@ -19,6 +19,7 @@ import torch
 from lingvo_amd.core import py_utils
 from lingvo_amd.core.base_layer import BaseLayer
 from lingvo_amd.core.nested_map import NestedMap
+from lingvo_amd.ops import attn_decode
 from lingvo_amd.ops import flash_attn
 
 
@@ -47,6 +48,10 @@ class MultiHeadedAttention(BaseLayer):
              'layers.py:3476 + batch_major_attention rope option).')
     p.Define('rope_tpl', None,
              'Optional RotaryPositionalEmbeddingLayer params override.')
+    p.Define('decode_impl', 'auto',
+             "ExtendStep/StreamStep attention route: 'auto' (HIP cached-"
+             "attention kernel on bf16 CUDA, composed torch elsewhere) or "
+             "'torch' (always composed; ops/attn_decode.py).")
     return p
 
   def __init__(self, params):
@@ -56,6 +61,10 @@ class MultiHeadedAttention(BaseLayer):
     nkv = p.num_kv_heads or n
     h = p.dim_per_head or (p.hidden_dim // n)
     self._n, self._nkv, self._h = n, nkv, h
+    # Route of the cached-attention steps; a plain attribute so that tools
+    # can alternate it on an instantiated layer.
+    assert p.decode_impl in ('auto', 'torch'), p.decode_impl
+    self.decode_impl = p.decode_impl
     # The gfx950 flash kernel supports dim_per_head 64/128 (checked at
     # the kernel boundary); other sizes run only on the CPU reference.
     # Fused QKV for self-attention: [D, (N + 2*NKV) * H].
@@ -203,30 +212,13 @@ class MultiHeadedAttention(BaseLayer):
                                dtype=torch.float32)).expand(b, c)
       q = self.rope.FProp(theta.rope, q, position=pos)
       k = self.rope.FProp(theta.rope, k, position=pos)
-    L = p.left_context if p.left_context >= 0 else state.key.shape[1]
     state.key[:, t0:t0 + c] = k.to(state.key.dtype)
     state.value[:, t0:t0 + c] = v.to(state.value.dtype)
     state.time_step = t0 + c
-    lo = max(0, t0 - L)
-    keys = state.key[:, lo:t0 + c]
-    values = state.value[:, lo:t0 + c]
-    group = n // nkv
-    kf = keys.float()
-    vf = values.float()
-    if group > 1:
-      kf = kf.repeat_interleave(group, dim=2)
-      vf = vf.repeat_interleave(group, dim=2)
-    logits = torch.einsum('bcnh,bsnh->bncs', q.float(), kf)
-    logits = logits / math.sqrt(h)
-    qpos = (t0 + torch.arange(c, device=x_chunk.device))[:, None]
-    kpos = (lo + torch.arange(kf.shape[1], device=x_chunk.device))[None, :]
-    mask = (kpos <= qpos) & (kpos >= qpos - L)
-    if p.rel_pos_bias:
-      d = (qpos - kpos).clamp(-p.rel_pos_clip, p.rel_pos_clip)           + p.rel_pos_clip
-      logits = logits + theta.rel_bias.float()[None, :, d]
-    logits = logits.masked_fill(~mask[None, None], -1e30)
-    probs = torch.softmax(logits, dim=-1)
-    ctx = torch.einsum('bncs,bsnh->bcnh', probs, vf)
+    ctx = attn_decode.cached_attention(
+        q, state.key, state.value, t0,
+        theta.rel_bias if p.rel_pos_bias else None, win_l=p.left_context,
+        bias_clip=p.rel_pos_clip, impl=self.decode_impl)
     ctx = ctx.reshape(b, c, n * h).to(x_chunk.dtype)
     post = py_utils.MatmulBias(ctx, theta.post_w,
                                theta.post_b if p.use_bias else None)
@@ -250,22 +242,11 @@ class MultiHeadedAttention(BaseLayer):
     cached_states.key[:, t:t + 1] = k.to(cached_states.key.dtype)
     cached_states.value[:, t:t + 1] = v.to(cached_states.value.dtype)
     cached_states.time_step = t + 1
-    keys = cached_states.key[:, :t + 1]
-    values = cached_states.value[:, :t + 1]
-    # One-step attention (GEMV-shaped); composed torch ops are fine here.
-    group = n // nkv
-    qf = q.reshape(b, n, h).float()
-    kf = keys.float().repeat_interleave(group, dim=2) if group > 1 \
-        else keys.float()
-    vf = values.float().repeat_interleave(group, dim=2) if group > 1 \
-        else values.float()
-    logits = torch.einsum('bnh,bsnh->bns', qf, kf) / math.sqrt(h)
-    if p.rel_pos_bias:
-      d = (t - torch.arange(t + 1, device=q.device)).clamp(
-          -p.rel_pos_clip, p.rel_pos_clip) + p.rel_pos_clip
-      logits = logits + theta.rel_bias.float()[:, d]
-    probs = torch.softmax(logits, dim=-1)
-    ctx = torch.einsum('bns,bsnh->bnh', probs, vf)
+    # One-step attention over the cache; left_context is not applied here.
+    ctx = attn_decode.cached_attention(
+        q, cached_states.key, cached_states.value, t,
+        theta.rel_bias if p.rel_pos_bias else None, win_l=-1,
+        bias_clip=p.rel_pos_clip, impl=self.decode_impl)
     ctx = ctx.reshape(b, 1, n * h).to(query_vec.dtype)
     post = torch.matmul(ctx, theta.post_w)
     if p.use_bias:

@@ -199,6 +199,17 @@ torch::Tensor rnnt_bwd(torch::Tensor logits, torch::Tensor logit_lengths,
                        int64_t blank);
 int64_t rnnt_max_label_len();
 
+// attn_decode.hip
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor key_cache,
+                          torch::Tensor value_cache,
+                          c10::optional<torch::Tensor> q_start_t,
+                          int64_t q_start,
+                          c10::optional<torch::Tensor> bias, int64_t win_l,
+                          int64_t bias_clip, double scale,
+                          int64_t num_splits);
+int64_t attn_decode_num_splits(int64_t B, int64_t NKV, int64_t keys,
+                               int64_t rows);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   RegisterInputPipeline(m);
   RegisterWpmTokenizer(m);
@@ -277,6 +288,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rnnt_bwd", &rnnt_bwd, "Transducer loss backward: dlogits");
   m.def("rnnt_max_label_len", &rnnt_max_label_len,
         "Largest label width U the transducer kernels support");
+  m.def("attn_decode", &attn_decode,
+        "KV-cache attention (ExtendStep/StreamStep): split-K decode kernel "
+        "+ combine",
+        py::arg("q"), py::arg("key_cache"), py::arg("value_cache"),
+        py::arg("q_start_t"), py::arg("q_start"), py::arg("bias"),
+        py::arg("win_l"), py::arg("bias_clip"), py::arg("scale"),
+        py::arg("num_splits") = 0);
+  m.def("attn_decode_num_splits", &attn_decode_num_splits,
+        "Split count attn_decode picks for (B, NKV, keys, rows = C * N/NKV)",
+        py::arg("B"), py::arg("NKV"), py::arg("keys"), py::arg("rows") = 1);
   m.def("s2d_fwd", &s2d_fwd, "Space-to-depth + pad (conv frontend)");
   m.def("topk_rows", &topk_rows, "Row-wise top-k (beam pruning, K12)");
   m.def("s2d_inv", &s2d_inv, "Inverse space-to-depth");
