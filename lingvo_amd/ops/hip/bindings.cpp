@@ -155,6 +155,18 @@ std::vector<torch::Tensor> attend_bwd(torch::Tensor dctx,
                                       torch::Tensor probs, torch::Tensor q,
                                       torch::Tensor enc, torch::Tensor denc,
                                       double scale);
+void attend_step_fwd(torch::Tensor q, torch::Tensor enc, torch::Tensor pad,
+                     double scale, torch::Tensor probs, torch::Tensor ctx,
+                     torch::Tensor ctx32, int64_t variant);
+void attend_step_bwd(torch::Tensor dctx_a, c10::optional<torch::Tensor> dctx_b,
+                     torch::Tensor probs, torch::Tensor ctx32,
+                     torch::Tensor enc, double scale, torch::Tensor dctx_out,
+                     torch::Tensor dl, torch::Tensor dq, int64_t variant);
+void attend_denc(torch::Tensor dl, torch::Tensor probs, torch::Tensor qs,
+                 torch::Tensor dctx, torch::Tensor out);
+int64_t attend_step_lds_bytes(int64_t s, int64_t d, bool bwd,
+                              int64_t variant);
+int64_t attend_denc_row_tile();
 int64_t attend_lds_limit();
 int64_t attend_lds_bytes(int64_t s, int64_t d, bool bwd);
 
@@ -270,6 +282,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Small-M MFMA GEMM (decode-step projections)");
   m.def("attend_fwd", &attend_fwd, "Fused dot-attention step fwd");
   m.def("attend_bwd", &attend_bwd, "Fused dot-attention step bwd");
+  m.def("attend_step_fwd", &attend_step_fwd,
+        "One-pass dot-attention step fwd into caller rows (probs, ctx, ctx32)",
+        py::arg("q"), py::arg("enc"), py::arg("pad"), py::arg("scale"),
+        py::arg("probs"), py::arg("ctx"), py::arg("ctx32"),
+        py::arg("variant") = 0);
+  m.def("attend_step_bwd", &attend_step_bwd,
+        "One-pass dot-attention step bwd without dEnc (dctx, dl, dq out)",
+        py::arg("dctx_a"), py::arg("dctx_b"), py::arg("probs"),
+        py::arg("ctx32"), py::arg("enc"), py::arg("scale"),
+        py::arg("dctx_out"), py::arg("dl"), py::arg("dq"),
+        py::arg("variant") = 0);
+  m.def("attend_denc", &attend_denc,
+        "dEnc of the whole recurrence from the stacked dl, probs, q, dctx");
+  m.def("attend_step_lds_bytes", &attend_step_lds_bytes,
+        "Dynamic LDS bytes attend_step_fwd/bwd ask for at (S, D, variant)");
+  m.def("attend_denc_row_tile", &attend_denc_row_tile,
+        "Rows of S one attend_denc workgroup owns");
   m.def("attend_lds_limit", &attend_lds_limit,
         "Dynamic LDS bytes an attend_* launch may ask for on this device");
   m.def("attend_lds_bytes", &attend_lds_bytes,

@@ -11,6 +11,9 @@
 //  - attend_fwd/attend_bwd: the dot-attention step (logits + masked
 //    softmax + context, and its full backward incl. dEnc accumulation)
 //    as one kernel per direction, one workgroup per batch row.
+//  - attend_step_fwd/attend_step_bwd/attend_denc: the same step reading
+//    enc once per kernel and leaving dEnc out; dEnc of the whole
+//    recurrence is one contraction over the step index after the loop.
 //
 // Consumed by models/asr.py DecoderRecurrence (custom autograd Function
 // that also batches all weight-gradient GEMMs across the L timesteps).
@@ -19,6 +22,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <atomic>
+#include <climits>
 
 #include "common.h"
 #include "mfma.h"
@@ -425,6 +429,345 @@ __global__ __launch_bounds__(256) void attend_bwd_kernel(
   }
 }
 
+
+// ---------------------------------------------------------------------------
+// Deferred-dEnc route: attend_step_fwd / attend_step_bwd / attend_denc.
+//
+// The step kernels read enc ONCE. One workgroup per batch row, NW waves,
+// each wave streams U rows of enc per iteration with the whole row slice
+// held in registers (NDV 512-column slices of 8 bf16 per lane), so the
+// dot product and the weighted accumulation use the same load.
+// ---------------------------------------------------------------------------
+
+// U rows x NDV slices of enc for this lane; rows past s_len and columns
+// past d read nothing and hold zeros.
+template <int NDV, int U>
+__device__ __forceinline__ void load_enc_rows(
+    const unsigned short* __restrict__ eb, int s0, int s_len, int d, int lane,
+    bf16x8 (&ev)[U][NDV]) {
+  const float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const bf16x8 zero = pack_bf16x8(z);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+#pragma unroll
+    for (int v = 0; v < NDV; ++v) {
+      const int i = lane * 8 + v * WAVE_SIZE * 8;
+      ev[u][v] = (s0 + u < s_len && i < d)
+                     ? load_bf16x8_bits(eb + (long)(s0 + u) * d + i)
+                     : zero;
+    }
+  }
+}
+
+// attend_step_fwd: attend_fwd with one pass over enc. Every wave keeps a
+// running max and an fp32 context partial rescaled to it (online softmax);
+// the raw logits go to LDS, and probs come from them with the final max
+// and sum exactly as in attend_fwd. ctx is written as fp32 and as bf16.
+// Dynamic LDS: logits (S f32) + NW*D f32 partials + NW f32.
+template <int NDV, int U, int NW>
+__global__ __launch_bounds__(NW * WAVE_SIZE) void attend_step_fwd_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ enc,
+    const float* __restrict__ pad, float* __restrict__ probs,
+    unsigned short* __restrict__ ctx, float* __restrict__ ctx32, int s_len,
+    int d, float scale) {
+  constexpr int NT = NW * WAVE_SIZE;
+  const int b = blockIdx.x;
+  const int wid = threadIdx.x / WAVE_SIZE;
+  const int lane = threadIdx.x & 63;
+  extern __shared__ char smem[];
+  float* logit_s = (float*)smem;                          // [S]
+  float* ctx_s = logit_s + s_len;                         // [NW][D]
+  float* red = ctx_s + NW * d;                            // [NW]
+
+  float qreg[NDV][8];
+#pragma unroll
+  for (int v = 0; v < NDV; ++v) {
+    const int i = lane * 8 + v * WAVE_SIZE * 8;
+    if (i < d) {
+      bf16x8 qv = load_bf16x8_bits(q + (long)b * d + i);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) qreg[v][j] = (float)qv[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) qreg[v][j] = 0.f;
+    }
+  }
+
+  const unsigned short* eb = enc + (long)b * s_len * d;
+  const float* padb = pad + (long)b * s_len;
+  float m = -1e30f;
+  float acc[NDV][8];
+#pragma unroll
+  for (int v = 0; v < NDV; ++v) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[v][j] = 0.f;
+  }
+  for (int s0 = wid * U; s0 < s_len; s0 += NW * U) {
+    bf16x8 ev[U][NDV];
+    load_enc_rows<NDV, U>(eb, s0, s_len, d, lane, ev);
+    // Rows past s_len are masked like padded ones: their weight stays
+    // <= 1 whatever the running max is, and their ev is zero.
+    float mask[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      mask[u] = (s0 + u >= s_len || padb[s0 + u] > 0.5f) ? -1e30f : 0.f;
+    }
+    float lg[U];
+    float mnew = m;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float part = 0.f;
+#pragma unroll
+      for (int v = 0; v < NDV; ++v) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) part += qreg[v][j] * (float)ev[u][v][j];
+      }
+      lg[u] = wave_reduce_sum(part) * scale + mask[u];
+      if (s0 + u < s_len) {
+        mnew = fmaxf(mnew, lg[u]);
+        if (lane == 0) logit_s[s0 + u] = lg[u];
+      }
+    }
+    const float f = __expf(m - mnew);
+    m = mnew;
+#pragma unroll
+    for (int v = 0; v < NDV; ++v) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[v][j] *= f;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const float p = __expf(lg[u] - mnew);
+#pragma unroll
+      for (int v = 0; v < NDV; ++v) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[v][j] += p * (float)ev[u][v][j];
+      }
+    }
+  }
+  if (lane == 0) red[wid] = m;
+  __syncthreads();
+  float lmax = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) lmax = fmaxf(lmax, red[w]);
+  {
+    const float wgt = __expf(m - lmax);
+#pragma unroll
+    for (int v = 0; v < NDV; ++v) {
+      const int i = lane * 8 + v * WAVE_SIZE * 8;
+      if (i < d) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ctx_s[wid * d + i + j] = acc[v][j] * wgt;
+      }
+    }
+  }
+  // Softmax over the LDS logits (block-wide), as in attend_fwd.
+  float lsum = 0.f;
+  for (int s = threadIdx.x; s < s_len; s += NT) {
+    float e = __expf(logit_s[s] - lmax);
+    logit_s[s] = e;
+    lsum += e;
+  }
+  lsum = wave_reduce_sum(lsum);
+  __syncthreads();  // every thread has read red[] as the max
+  if (lane == 0) red[wid] = lsum;
+  __syncthreads();
+  lsum = 0.f;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) lsum += red[w];
+  const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
+  for (int s = threadIdx.x; s < s_len; s += NT) {
+    probs[(long)b * s_len + s] = logit_s[s] * inv;
+  }
+  for (int i = threadIdx.x; i < d; i += NT) {
+    float c = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) c += ctx_s[w * d + i];
+    c *= inv;
+    ctx32[(long)b * d + i] = c;
+    ctx[(long)b * d + i] = float_to_bf16_bits(c);
+  }
+}
+
+// attend_step_bwd: per batch row b, with dctx = bf16(dctx_a + dctx_b)
+// (dctx_b optional, row stride ldb) stored to dctx_out:
+//   t = dot(dctx, ctx32[b])          (= sum_s probs[s]*dprobs[s])
+//   dprobs[s] = dot(dctx, enc[b,s]); dl[s] = probs[s]*(dprobs[s]-t)*scale
+//   dq[b] = sum_s dl[s]*enc[b,s]
+// dl goes to dl_out for attend_denc; enc is read once and dEnc is not
+// touched. Dynamic LDS: dctx (D f32) + NW*D f32 partials + NW f32.
+template <int NDV, int U, int NW>
+__global__ __launch_bounds__(NW * WAVE_SIZE) void attend_step_bwd_kernel(
+    const unsigned short* __restrict__ dctx_a,
+    const unsigned short* __restrict__ dctx_b, long ldb,
+    const float* __restrict__ probs, const float* __restrict__ ctx32,
+    const unsigned short* __restrict__ enc,
+    unsigned short* __restrict__ dctx_out, float* __restrict__ dl_out,
+    unsigned short* __restrict__ dq, int s_len, int d, float scale) {
+  constexpr int NT = NW * WAVE_SIZE;
+  const int b = blockIdx.x;
+  const int wid = threadIdx.x / WAVE_SIZE;
+  const int lane = threadIdx.x & 63;
+  extern __shared__ char smem[];
+  float* dc_s = (float*)smem;                             // [D]
+  float* dq_s = dc_s + d;                                 // [NW][D]
+  float* red = dq_s + NW * d;                             // [NW]
+
+  float t_part = 0.f;
+  for (int i = threadIdx.x; i < d; i += NT) {
+    unsigned short bits = dctx_a[(long)b * d + i];
+    if (dctx_b != nullptr) {
+      bits = float_to_bf16_bits(bf16_bits_to_float(bits) +
+                                bf16_bits_to_float(dctx_b[(long)b * ldb + i]));
+    }
+    dctx_out[(long)b * d + i] = bits;
+    const float v = bf16_bits_to_float(bits);
+    dc_s[i] = v;
+    t_part += v * ctx32[(long)b * d + i];
+  }
+  const float t = block_reduce_sum<NW>(t_part, red);  // syncs: dc_s visible
+
+  float dcreg[NDV][8];
+#pragma unroll
+  for (int v = 0; v < NDV; ++v) {
+    const int i = lane * 8 + v * WAVE_SIZE * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dcreg[v][j] = i < d ? dc_s[i + j] : 0.f;
+  }
+
+  const unsigned short* eb = enc + (long)b * s_len * d;
+  const float* pb = probs + (long)b * s_len;
+  float* dlb = dl_out + (long)b * s_len;
+  float acc[NDV][8];
+#pragma unroll
+  for (int v = 0; v < NDV; ++v) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[v][j] = 0.f;
+  }
+  for (int s0 = wid * U; s0 < s_len; s0 += NW * U) {
+    bf16x8 ev[U][NDV];
+    load_enc_rows<NDV, U>(eb, s0, s_len, d, lane, ev);
+    float pv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) pv[u] = s0 + u < s_len ? pb[s0 + u] : 0.f;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float part = 0.f;
+#pragma unroll
+      for (int v = 0; v < NDV; ++v) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) part += dcreg[v][j] * (float)ev[u][v][j];
+      }
+      const float dlv = pv[u] * (wave_reduce_sum(part) - t) * scale;
+      if (lane == u && s0 + u < s_len) dlb[s0 + u] = dlv;
+#pragma unroll
+      for (int v = 0; v < NDV; ++v) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[v][j] += dlv * (float)ev[u][v][j];
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < NDV; ++v) {
+    const int i = lane * 8 + v * WAVE_SIZE * 8;
+    if (i < d) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dq_s[wid * d + i + j] = acc[v][j];
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < d; i += NT) {
+    float c = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) c += dq_s[w * d + i];
+    dq[(long)b * d + i] = float_to_bf16_bits(c);
+  }
+}
+
+// attend_denc: dEnc of the whole recurrence, once after the loop:
+//   denc[b,s,:] = sum_l dl[l,b,s]*q[l,b,:] + probs[l,b,s]*dctx[l,b,:]
+// Grid: (B * ceil(S/32), ceil(D/512)); block 256 = 4 waves. A workgroup
+// owns 32 rows s of one batch row b and 512 columns; wave w owns rows
+// 8w..8w+7, a lane owns 8 columns of each, 64 fp32 accumulators. The
+// per-row scalars (dl, probs) of 64 steps l at a time are staged in LDS and
+// read as wave-wide broadcasts; the q / dctx rows come from L2. The sum
+// over l runs in a fixed order in fp32 and every element is stored once.
+constexpr int kDencRows = 8;                 // rows per wave
+constexpr int kDencTile = 4 * kDencRows;     // rows per workgroup
+constexpr int kDencSteps = 64;               // steps l staged per LDS fill
+
+__device__ __forceinline__ void store_denc(float* p, const float* a) {
+  floatx4* pv = reinterpret_cast<floatx4*>(p);
+  pv[0] = floatx4{a[0], a[1], a[2], a[3]};
+  pv[1] = floatx4{a[4], a[5], a[6], a[7]};
+}
+
+__device__ __forceinline__ void store_denc(unsigned short* p, const float* a) {
+  ushortx8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = float_to_bf16_bits(a[j]);
+  *reinterpret_cast<ushortx8*>(p) = o;
+}
+
+template <typename OutT>
+__global__ __launch_bounds__(256) void attend_denc_kernel(
+    const float* __restrict__ dl, const float* __restrict__ probs,
+    const unsigned short* __restrict__ qs,
+    const unsigned short* __restrict__ dctx, OutT* __restrict__ out,
+    int l_total, int b_total, int s_len, int d, int s_tiles) {
+  const int b = blockIdx.x / s_tiles;
+  const int s_base = (blockIdx.x % s_tiles) * kDencTile;
+  const int wid = threadIdx.x / WAVE_SIZE;
+  const int lane = threadIdx.x & 63;
+  const int c0 = blockIdx.y * WAVE_SIZE * 8 + lane * 8;
+  __shared__ float sc[kDencSteps][kDencTile][2];          // {dl, probs}
+
+  float acc[kDencRows][8];
+#pragma unroll
+  for (int r = 0; r < kDencRows; ++r) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[r][j] = 0.f;
+  }
+  for (int l0 = 0; l0 < l_total; l0 += kDencSteps) {
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < kDencSteps * kDencTile; idx += 256) {
+      const int ll = idx / kDencTile, r = idx % kDencTile;
+      const int l = l0 + ll, s = s_base + r;
+      const bool ok = l < l_total && s < s_len;
+      const long off = ((long)l * b_total + b) * s_len + s;
+      sc[ll][r][0] = ok ? dl[off] : 0.f;
+      sc[ll][r][1] = ok ? probs[off] : 0.f;
+    }
+    __syncthreads();
+    if (c0 < d) {
+      const int l_cnt = min(kDencSteps, l_total - l0);
+#pragma unroll 4
+      for (int ll = 0; ll < l_cnt; ++ll) {
+        const long off = ((long)(l0 + ll) * b_total + b) * d + c0;
+        const bf16x8 qv = load_bf16x8_bits(qs + off);
+        const bf16x8 dv = load_bf16x8_bits(dctx + off);
+#pragma unroll
+        for (int r = 0; r < kDencRows; ++r) {
+          const float a = sc[ll][wid * kDencRows + r][0];
+          const float p = sc[ll][wid * kDencRows + r][1];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            acc[r][j] += a * (float)qv[j];
+            acc[r][j] += p * (float)dv[j];
+          }
+        }
+      }
+    }
+  }
+  if (c0 < d) {
+#pragma unroll
+    for (int r = 0; r < kDencRows; ++r) {
+      const int s = s_base + wid * kDencRows + r;
+      if (s < s_len) store_denc(out + ((long)b * s_len + s) * d + c0, acc[r]);
+    }
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -595,3 +938,199 @@ int64_t attend_lds_limit() { return (int64_t)lds_limit_bytes(); }
 int64_t attend_lds_bytes(int64_t s, int64_t d, bool bwd) {
   return (int64_t)(bwd ? attend_bwd_lds(s, d) : attend_fwd_lds(s, d));
 }
+
+// ---------------------------------------------------------------------------
+// Deferred-dEnc route
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// variant: 0 auto, 1..4 = (rows per wave iteration, waves) of
+// (4,4) (8,4) (4,8) (8,8). 8 rows of more than two 512-column slices do
+// not fit the register file, so those variants stop at D = 1024. Returns
+// false for a variant that does not exist at this D.
+bool step_variant(int64_t variant, int64_t d, int* u, int* nw) {
+  if (variant == 0) variant = d <= 2 * WAVE_SIZE * 8 ? 3 : 1;
+  if (variant < 1 || variant > 4) return false;
+  *u = (variant == 2 || variant == 4) ? 8 : 4;
+  *nw = variant >= 3 ? 8 : 4;
+  return *u == 4 || d <= 2 * WAVE_SIZE * 8;
+}
+
+size_t attend_step_fwd_lds(int64_t s, int64_t d, int nw) {
+  return (size_t)s * 4 + (size_t)nw * d * 4 + (size_t)nw * 4;
+}
+
+size_t attend_step_bwd_lds(int64_t s, int64_t d, int nw) {
+  (void)s;
+  return (size_t)d * 4 + (size_t)nw * d * 4 + (size_t)nw * 4;
+}
+
+// A [rows, cols] tensor of dtype st whose rows are dense (a row of a
+// larger contiguous stack is).
+bool cuda_rows(const torch::Tensor& t, torch::ScalarType st, int64_t rows,
+               int64_t cols) {
+  return t.is_cuda() && t.scalar_type() == st && t.dim() == 2 &&
+         t.size(0) == rows && t.size(1) == cols && t.is_contiguous();
+}
+
+#define LV_STEP_CASE(NDV, U, NW, KERNEL, ...)                               \
+  if (ndv == NDV && u == U && nw == NW) {                                   \
+    hipLaunchKernelGGL((KERNEL<NDV, U, NW>), dim3(b), dim3(NW * WAVE_SIZE), \
+                       shmem, stream, __VA_ARGS__);                         \
+  } else
+
+#define LV_STEP_NDV(NDV, KERNEL, ...)         \
+  LV_STEP_CASE(NDV, 4, 4, KERNEL, __VA_ARGS__) \
+  LV_STEP_CASE(NDV, 8, 4, KERNEL, __VA_ARGS__) \
+  LV_STEP_CASE(NDV, 4, 8, KERNEL, __VA_ARGS__) \
+  LV_STEP_CASE(NDV, 8, 8, KERNEL, __VA_ARGS__)
+
+#define LV_STEP_DISPATCH(KERNEL, ...)                          \
+  LV_STEP_NDV(1, KERNEL, __VA_ARGS__)                          \
+  LV_STEP_NDV(2, KERNEL, __VA_ARGS__)                          \
+  LV_STEP_CASE(3, 4, 4, KERNEL, __VA_ARGS__)                   \
+  LV_STEP_CASE(3, 4, 8, KERNEL, __VA_ARGS__)                   \
+  LV_STEP_CASE(4, 4, 4, KERNEL, __VA_ARGS__)                   \
+  LV_STEP_CASE(4, 4, 8, KERNEL, __VA_ARGS__) {                 \
+    TORCH_CHECK(false, "no kernel for ndv=", ndv, " u=", u, " nw=", nw); \
+  }
+
+}  // namespace
+
+void attend_step_fwd(torch::Tensor q, torch::Tensor enc, torch::Tensor pad,
+                     double scale, torch::Tensor probs, torch::Tensor ctx,
+                     torch::Tensor ctx32, int64_t variant) {
+  check_attend_q_enc(q, enc);
+  const int b = q.size(0), d = q.size(1);
+  const int s = enc.size(1);
+  TORCH_CHECK(cuda_contig(pad, torch::kFloat32) && pad.dim() == 2 &&
+              pad.size(0) == b && pad.size(1) == s,
+              "pad must be CUDA contiguous fp32 [B,S]");
+  TORCH_CHECK(cuda_rows(probs, torch::kFloat32, b, s),
+              "probs must be CUDA contiguous fp32 [B,S]");
+  TORCH_CHECK(cuda_rows(ctx, torch::kBFloat16, b, d),
+              "ctx must be CUDA contiguous bf16 [B,D]");
+  TORCH_CHECK(cuda_rows(ctx32, torch::kFloat32, b, d),
+              "ctx32 must be CUDA contiguous fp32 [B,D]");
+  int u = 0, nw = 0;
+  TORCH_CHECK(step_variant(variant, d, &u, &nw),
+              "variant in 0..4, and 2 or 4 only for D <= 1024");
+  const size_t shmem = attend_step_fwd_lds(s, d, nw);
+  TORCH_CHECK(shmem <= lds_limit_bytes(), "attend_step_fwd: S=", s, " D=", d,
+              " needs ", shmem, " bytes of LDS, over the device limit");
+  const int ndv = cdiv(d, WAVE_SIZE * 8);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  LV_STEP_DISPATCH(attend_step_fwd_kernel,
+                   (const unsigned short*)q.data_ptr(),
+                   (const unsigned short*)enc.data_ptr(),
+                   pad.data_ptr<float>(), probs.data_ptr<float>(),
+                   (unsigned short*)ctx.data_ptr(), ctx32.data_ptr<float>(),
+                   s, d, (float)scale)
+  LV_CHECK_HIP(hipGetLastError());
+}
+
+void attend_step_bwd(torch::Tensor dctx_a, c10::optional<torch::Tensor> dctx_b,
+                     torch::Tensor probs, torch::Tensor ctx32,
+                     torch::Tensor enc, double scale, torch::Tensor dctx_out,
+                     torch::Tensor dl, torch::Tensor dq, int64_t variant) {
+  check_attend_q_enc(dctx_a, enc);
+  const int b = dctx_a.size(0), d = dctx_a.size(1);
+  const int s = enc.size(1);
+  const unsigned short* bp = nullptr;
+  long ldb = 0;
+  if (dctx_b.has_value()) {
+    const torch::Tensor& t = *dctx_b;
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
+                t.dim() == 2 && t.size(0) == b && t.size(1) == d &&
+                t.stride(1) == 1 && t.stride(0) >= d,
+                "dctx_b must be CUDA bf16 [B,D] with unit column stride");
+    bp = (const unsigned short*)t.data_ptr();
+    ldb = t.stride(0);
+  }
+  TORCH_CHECK(cuda_rows(probs, torch::kFloat32, b, s),
+              "probs must be CUDA contiguous fp32 [B,S]");
+  TORCH_CHECK(cuda_rows(ctx32, torch::kFloat32, b, d),
+              "ctx32 must be CUDA contiguous fp32 [B,D]");
+  TORCH_CHECK(cuda_rows(dctx_out, torch::kBFloat16, b, d),
+              "dctx_out must be CUDA contiguous bf16 [B,D]");
+  TORCH_CHECK(cuda_rows(dl, torch::kFloat32, b, s),
+              "dl must be CUDA contiguous fp32 [B,S]");
+  TORCH_CHECK(cuda_rows(dq, torch::kBFloat16, b, d),
+              "dq must be CUDA contiguous bf16 [B,D]");
+  int u = 0, nw = 0;
+  TORCH_CHECK(step_variant(variant, d, &u, &nw),
+              "variant in 0..4, and 2 or 4 only for D <= 1024");
+  const size_t shmem = attend_step_bwd_lds(s, d, nw);
+  TORCH_CHECK(shmem <= lds_limit_bytes(), "attend_step_bwd: S=", s, " D=", d,
+              " needs ", shmem, " bytes of LDS, over the device limit");
+  const int ndv = cdiv(d, WAVE_SIZE * 8);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  LV_STEP_DISPATCH(attend_step_bwd_kernel,
+                   (const unsigned short*)dctx_a.data_ptr(), bp, ldb,
+                   probs.data_ptr<float>(), ctx32.data_ptr<float>(),
+                   (const unsigned short*)enc.data_ptr(),
+                   (unsigned short*)dctx_out.data_ptr(),
+                   dl.data_ptr<float>(), (unsigned short*)dq.data_ptr(), s,
+                   d, (float)scale)
+  LV_CHECK_HIP(hipGetLastError());
+}
+
+void attend_denc(torch::Tensor dl, torch::Tensor probs, torch::Tensor qs,
+                 torch::Tensor dctx, torch::Tensor out) {
+  TORCH_CHECK(cuda_contig(dl, torch::kFloat32) && dl.dim() == 3,
+              "dl must be CUDA contiguous fp32 [L,B,S]");
+  const int64_t l = dl.size(0), b = dl.size(1), s = dl.size(2);
+  TORCH_CHECK(l >= 1 && b >= 1 && s >= 1, "L, B, S >= 1");
+  TORCH_CHECK(cuda_contig(probs, torch::kFloat32) &&
+              probs.sizes() == dl.sizes(),
+              "probs must be CUDA contiguous fp32 [L,B,S]");
+  TORCH_CHECK(cuda_contig(qs, torch::kBFloat16) && qs.dim() == 3 &&
+              qs.size(0) == l && qs.size(1) == b,
+              "qs must be CUDA contiguous bf16 [L,B,D]");
+  const int64_t d = qs.size(2);
+  TORCH_CHECK(d >= 8 && d % 8 == 0, "D % 8 == 0");
+  TORCH_CHECK(d <= kAttendMaxD, "D <= 2048");
+  TORCH_CHECK(cuda_contig(dctx, torch::kBFloat16) &&
+              dctx.sizes() == qs.sizes(),
+              "dctx must be CUDA contiguous bf16 [L,B,D]");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 3 &&
+              out.size(0) == b && out.size(1) == s && out.size(2) == d &&
+              (out.scalar_type() == torch::kFloat32 ||
+               out.scalar_type() == torch::kBFloat16),
+              "out must be CUDA contiguous fp32 or bf16 [B,S,D]");
+  TORCH_CHECK(l <= INT_MAX && b <= INT_MAX && s <= INT_MAX, "sizes fit int");
+  const int64_t s_tiles = (s + kDencTile - 1) / kDencTile;
+  TORCH_CHECK(b * s_tiles <= INT_MAX, "B * ceil(S/32) fits the grid");
+  const dim3 grid((unsigned)(b * s_tiles), cdiv(d, WAVE_SIZE * 8));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (out.scalar_type() == torch::kFloat32) {
+    hipLaunchKernelGGL(attend_denc_kernel<float>, grid, dim3(256), 0, stream,
+                       dl.data_ptr<float>(), probs.data_ptr<float>(),
+                       (const unsigned short*)qs.data_ptr(),
+                       (const unsigned short*)dctx.data_ptr(),
+                       out.data_ptr<float>(), (int)l, (int)b, (int)s, (int)d,
+                       (int)s_tiles);
+  } else {
+    hipLaunchKernelGGL(attend_denc_kernel<unsigned short>, grid, dim3(256), 0,
+                       stream, dl.data_ptr<float>(), probs.data_ptr<float>(),
+                       (const unsigned short*)qs.data_ptr(),
+                       (const unsigned short*)dctx.data_ptr(),
+                       (unsigned short*)out.data_ptr(), (int)l, (int)b,
+                       (int)s, (int)d, (int)s_tiles);
+  }
+  LV_CHECK_HIP(hipGetLastError());
+}
+
+// Dynamic LDS bytes attend_step_fwd / attend_step_bwd ask for at (S, D)
+// with this variant, and the rows of s one attend_denc workgroup owns.
+int64_t attend_step_lds_bytes(int64_t s, int64_t d, bool bwd,
+                              int64_t variant) {
+  int u = 0, nw = 0;
+  TORCH_CHECK(step_variant(variant, d, &u, &nw),
+              "variant in 0..4, and 2 or 4 only for D <= 1024");
+  return (int64_t)(bwd ? attend_step_bwd_lds(s, d, nw)
+                       : attend_step_fwd_lds(s, d, nw));
+}
+
+int64_t attend_denc_row_tile() { return kDencTile; }

@@ -13,6 +13,14 @@ WHOLE L-step recurrence:
 
 Reference semantics: lingvo/tasks/asr/decoder.py teacher-forced LAS
 loop; decode one-step einsums batch_major_attention.py:920,1069.
+
+Two routes for the attention step (attend_route):
+  - 'deferred' (the default, 'auto'): attend_step_fwd / attend_step_bwd
+    read enc once per step and write straight into rows of the [L,B,*]
+    stacks; dEnc is one contraction over the step index after the loop
+    (attend_denc), written once in enc's dtype.
+  - 'accumulate': attend_fwd / attend_bwd, which add every step's dEnc
+    increment into an fp32 [B,S,D] buffer.
 """
 
 from __future__ import annotations
@@ -29,7 +37,7 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, emb_gates, w_cm0, b1, wm1, wq, enc, enc_pad, fgb, cap,
-              src_dim):
+              src_dim, deferred):
     ext = _loader.get_ext(required=True)
     B, L, G4 = emb_gates.shape
     H = G4 // 4
@@ -54,6 +62,11 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
     zeros_h = torch.zeros(B, H, dtype=dt, device=dev)
     c0, m0, c1, m1 = zeros_h, zeros_h, zeros_h, zeros_h
     ctxv = torch.zeros(B, D, dtype=dt, device=dev)
+    if deferred:
+      S = enc_b.shape[1]
+      ctx_st = torch.empty(L, B, D, dtype=dt, device=dev)
+      ctx32_st = torch.empty(L, B, D, dtype=torch.float32, device=dev)
+      probs_st = torch.empty(L, B, S, dtype=torch.float32, device=dev)
     for t in range(L):
       g0 = gates0[t]
       ext.smallm_gemm(ctxv, w1t, eg_t[t], g0, src_dim, 0, 1.0, 2)
@@ -65,22 +78,30 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
       c1, m1 = ext.lstm_gates_fwd(g1, c1, fgb, cap)
       q = qs[t]
       ext.smallm_gemm(m1, wqt, None, q, H, 0, 1.0, 0)
-      p, ctxv = ext.attend_fwd(q, enc_b, pad_f, scale)
+      if deferred:
+        ctxv = ctx_st[t]
+        ext.attend_step_fwd(q, enc_b, pad_f, scale, probs_st[t], ctxv,
+                            ctx32_st[t])
+      else:
+        p, ctxv = ext.attend_fwd(q, enc_b, pad_f, scale)
+        ctxs.append(ctxv)
+        probs_l.append(p)
       c0s.append(c0)
       m0s.append(m0)
       c1s.append(c1)
       m1s.append(m1)
-      ctxs.append(ctxv)
-      probs_l.append(p)
 
     m1_st = torch.stack(m1s)                  # [L, B, H]
-    ctx_st = torch.stack(ctxs)                # [L, B, D]
+    if not deferred:
+      ctx_st = torch.stack(ctxs)              # [L, B, D]
+      probs_st = torch.stack(probs_l)
+      ctx32_st = torch.empty(0, device=dev)
     ctx.save_for_backward(
         emb_gates_b, w_cm0, wm1, wq, enc_b, pad_f, gates0, gates1, qs,
         torch.stack(c0s), torch.stack(m0s), torch.stack(c1s), m1_st,
-        ctx_st, torch.stack(probs_l))
+        ctx_st, probs_st, ctx32_st)
     ctx.cfg = (fgb, cap, src_dim, scale, b1.dtype, enc.dtype,
-               emb_gates.dtype)
+               emb_gates.dtype, deferred)
     out = torch.cat(
         [m1_st.permute(1, 0, 2), ctx_st.permute(1, 0, 2)], dim=-1)
     return out  # [B, L, H + D]
@@ -89,8 +110,9 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
   def backward(ctx, dout):
     ext = _loader.get_ext(required=True)
     (emb_gates_b, w_cm0, wm1, wq, enc_b, pad_f, gates0, gates1, qs, c0s,
-     m0s, c1s, m1s, ctxs, probs) = ctx.saved_tensors
-    fgb, cap, src_dim, scale, b1_dtype, enc_dtype, eg_dtype = ctx.cfg
+     m0s, c1s, m1s, ctxs, probs, ctx32s) = ctx.saved_tensors
+    (fgb, cap, src_dim, scale, b1_dtype, enc_dtype, eg_dtype,
+     deferred) = ctx.cfg
     L, B, G4 = gates0.shape
     H = G4 // 4
     D = qs.shape[-1]
@@ -101,13 +123,19 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
     wm1_b = wm1.to(dt).contiguous()           # [2H, 4H]
     wq_b = wq.to(dt).contiguous()             # [H, D]
 
-    denc = torch.zeros(B, enc_b.shape[1], D, dtype=torch.float32,
-                       device=dev)
+    S = enc_b.shape[1]
+    if deferred:
+      dctx_st = torch.empty(L, B, D, dtype=dt, device=dev)
+      dl_st = torch.empty(L, B, S, dtype=torch.float32, device=dev)
+    else:
+      denc = torch.zeros(B, S, D, dtype=torch.float32, device=dev)
     dgates0 = torch.empty(L, B, G4, dtype=dt, device=dev)
     dgates1 = torch.empty(L, B, G4, dtype=dt, device=dev)
     dqs = torch.empty(L, B, D, dtype=dt, device=dev)
     zeros_h = torch.zeros(B, H, dtype=dt, device=dev)
-    dctx_carry = torch.zeros(B, D, dtype=dt, device=dev)
+    # deferred: the dcm[:, :src_dim] view, added inside attend_step_bwd.
+    dctx_carry = None if deferred else \
+        torch.zeros(B, D, dtype=dt, device=dev)
     dm0_carry = zeros_h
     dm1_carry = zeros_h
     dc0_carry: Optional[torch.Tensor] = None
@@ -119,10 +147,15 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
     dm1_parts = dout_t[:, :, :H].contiguous()   # [L, B, H]
     dctx_parts = dout_t[:, :, H:].contiguous()  # [L, B, D]
     for t in range(L - 1, -1, -1):
-      dctx_total = dctx_parts[t] + dctx_carry
-      dq = ext.attend_bwd(dctx_total, probs[t], qs[t], enc_b, denc,
-                          scale)[0]
-      dqs[t] = dq
+      if deferred:
+        dq = dqs[t]
+        ext.attend_step_bwd(dctx_parts[t], dctx_carry, probs[t], ctx32s[t],
+                            enc_b, scale, dctx_st[t], dl_st[t], dq)
+      else:
+        dctx_total = dctx_parts[t] + dctx_carry
+        dq = ext.attend_bwd(dctx_total, probs[t], qs[t], enc_b, denc,
+                            scale)[0]
+        dqs[t] = dq
       pre_m1 = dm1_parts[t] + dm1_carry
       # dm1_total = dq @ wq^T + (out grad + carry)
       ext.smallm_gemm(dq, wq_b, pre_m1, dm1_total, D, 0, 1.0, 2)
@@ -137,7 +170,9 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
           gates0[t], c0_prev, c0s[t], dm0_total, dc0_carry, fgb, cap)
       dgates0[t] = dg0
       ext.smallm_gemm(dg0, w_cm0_b, None, dcm, G4, 0, 1.0, 0)
-      dctx_carry = dcm[:, :src_dim].contiguous()
+      dctx_carry = dcm[:, :src_dim]
+      if not deferred:
+        dctx_carry = dctx_carry.contiguous()
       dm0_carry = dcm[:, src_dim:].contiguous()
       dm1_carry = dmm[:, H:].contiguous()
 
@@ -156,20 +191,33 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
     db1 = dgates1.float().sum(dim=(0, 1)).to(b1_dtype)
     dwq = (m1s.reshape(L * B, H).t() @ dqs.reshape(L * B, D)).to(wq.dtype)
     demb_gates = dgates0.permute(1, 0, 2).to(eg_dtype)
+    if deferred:
+      denc = torch.empty(
+          B, S, D, device=dev,
+          dtype=dt if enc_dtype == torch.bfloat16 else torch.float32)
+      ext.attend_denc(dl_st, probs, qs, dctx_st, denc)
     return (demb_gates, dw_cm0, db1, dwm1, dwq, denc.to(enc_dtype),
-            None, None, None, None)
+            None, None, None, None, None)
 
 
 def decoder_recurrence(emb_gates: torch.Tensor, w_cm0: torch.Tensor,
                        b1: torch.Tensor, wm1: torch.Tensor,
                        wq: torch.Tensor, enc: torch.Tensor,
                        enc_pad: torch.Tensor, fgb: float, cap: float,
-                       src_dim: int) -> torch.Tensor:
+                       src_dim: int,
+                       attend_route: str = 'auto') -> torch.Tensor:
   """Teacher-forced 2-layer LSTM + dot-attention decoder over L steps.
 
   emb_gates [B,L,4H]: per-step precomputed gate contribution of the
   token embedding INCLUDING the layer-0 bias. w_cm0 [(src+H), 4H],
   wm1 [2H, 4H], b1 [4H], wq [H, src]. Returns [B, L, H + src]
-  (cat of m1 and attention context per step)."""
+  (cat of m1 and attention context per step).
+
+  attend_route: 'deferred' reads enc once per step and forms dEnc in one
+  kernel after the loop; 'accumulate' adds every step's increment into an
+  fp32 dEnc buffer; 'auto' is 'deferred'."""
+  if attend_route not in ('auto', 'deferred', 'accumulate'):
+    raise ValueError(f'unknown attend_route {attend_route!r}')
   return _DecoderRecurrenceFn.apply(emb_gates, w_cm0, b1, wm1, wq, enc,
-                                    enc_pad, fgb, cap, src_dim)
+                                    enc_pad, fgb, cap, src_dim,
+                                    attend_route != 'accumulate')
