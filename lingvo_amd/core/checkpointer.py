@@ -306,6 +306,11 @@ class ShardedCheckpointer(Checkpointer):
         f.write(f'num_shards: {self._num_shards}\n')
       os.replace(tmp, state)
       self._GCShards(step)
+    if dist.is_initialized():
+      # The state file is committed before any rank returns: a Restore()
+      # right after Save() on another rank must not find it missing and
+      # fall back to guessing the step from the shard file names.
+      dist.barrier()
     self._last_save_time = time.time()
     self._last_save_step = step
     return path

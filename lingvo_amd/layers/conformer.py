@@ -376,11 +376,111 @@ class _Conv3x3S2Nhwc(torch.autograd.Function):
     return dx, dw, dbias
 
 
+class _Conv1S2d(torch.autograd.Function):
+  """relu(conv1(x) + b1) for the Cin=1 3x3/s2 conv, written straight into
+  the padded space-to-depth buffer X [B, Ho+1, Wo+1, 4C] that conv2 reads
+  (conv1_s2d_fwd). Neither the conv1 activation in NHWC nor the unfold
+  columns exist. X is exactly the ReLU output, so it carries the mask:
+  backward (conv1_s2d_bwd) reads dX and X in s2d layout plus the features
+  and returns fp32 dw1 / db1. The features get no gradient."""
+
+  @staticmethod
+  def forward(ctx, x, w1, b1):
+    """x [B,T,F]; w1 [3,3,1,C]; b1 [C] -> X [B, Ho+1, Wo+1, 4C]."""
+    from lingvo_amd.ops import _loader
+    X = _loader.get_ext(required=True).conv1_s2d_fwd(
+        x, w1.reshape(9, w1.shape[-1]).contiguous(), b1.contiguous())
+    ctx.save_for_backward(X, x)
+    ctx.w_shape = w1.shape
+    return X
+
+  @staticmethod
+  def backward(ctx, dX):
+    from lingvo_amd.ops import _loader
+    X, x = ctx.saved_tensors
+    dw1, db1 = _loader.get_ext(required=True).conv1_s2d_bwd(
+        dX.contiguous(), X, x)
+    return (None, dw1.to(X.dtype).reshape(ctx.w_shape), db1.to(X.dtype))
+
+
+class _Conv3x3S2ReluFromS2d(torch.autograd.Function):
+  """relu(_Conv3x3S2Nhwc) on an input that already is the padded s2d
+  buffer X [B, Ho+1, Wo+1, 4C]; the gradient is returned in the same
+  layout. Same four cell GEMMs as _Conv3x3S2Nhwc, with the output side
+  fused: the bias rides in the first GEMM, unpad_relu slices and
+  rectifies in one pass, pad_scatter_relu_bwd masks, pads and sums the
+  bias gradient in one pass, and dX starts from cell (0,0) with beta = 0
+  (that cell covers every channel block at row offset 0) so no zero-filled
+  dX is needed."""
+
+  @staticmethod
+  def forward(ctx, X4, w, bias):
+    from lingvo_amd.ops import _loader
+    ext = _loader.get_ext(required=True)
+    B, Hp, Wp, C4 = X4.shape
+    C, Co = C4 // 4, w.shape[3]
+    Rp = B * Hp * Wp
+    base = Wp + 1
+    X = X4.reshape(Rp, C4)
+    # Rows [0, base) of O are border cells: no GEMM writes them and
+    # unpad_relu reads only hp, wp >= 1, so they stay unwritten.
+    O = X.new_empty(Rp, Co)
+    wb = w.to(X.dtype)
+    for n, ((dtau, dphi), taps) in enumerate(_Conv3x3S2Nhwc.CELLS):
+      off = dtau * Wp + dphi
+      blks = sorted(t[2] for t in taps)
+      k0, k1 = blks[0] * C, (blks[-1] + 1) * C
+      wc = _Conv3x3S2Nhwc._cell_weight(wb, taps)
+      A = X[base + off:Rp + off, k0:k1]
+      if n == 0:
+        torch.addmm(bias.to(X.dtype), A, wc, out=O[base:])
+      else:
+        O[base:].addmm_(A, wc)
+    y = ext.unpad_relu(O.reshape(B, Hp, Wp, Co))
+    ctx.save_for_backward(X, w, y)
+    ctx.bias_dtype = bias.dtype
+    return y
+
+  @staticmethod
+  def backward(ctx, dout):
+    from lingvo_amd.ops import _loader
+    ext = _loader.get_ext(required=True)
+    X, w, y = ctx.saved_tensors
+    B, Ho, Wo, Co = y.shape
+    Hp, Wp = Ho + 1, Wo + 1
+    C = X.shape[1] // 4
+    Rp = B * Hp * Wp
+    base = Wp + 1
+    dO, db = ext.pad_scatter_relu_bwd(dout.contiguous(), y)
+    dO = dO.reshape(Rp, Co)
+    dX = torch.empty_like(X)
+    dX[:base].zero_()
+    dw = torch.empty_like(w)
+    wb = w.to(dO.dtype)
+    # Cell (0,0) first: beta = 0 over rows [base, Rp), all 4C channels.
+    for (dtau, dphi), taps in reversed(_Conv3x3S2Nhwc.CELLS):
+      off = dtau * Wp + dphi
+      blks = sorted(t[2] for t in taps)
+      k0, k1 = blks[0] * C, (blks[-1] + 1) * C
+      g = X[base + off:Rp + off, k0:k1].t() @ dO[base:]
+      for i, (dt, df, _) in enumerate(sorted(taps, key=lambda t: t[2])):
+        dw[dt, df] = g[i * C:(i + 1) * C].to(w.dtype)
+      wc_t = _Conv3x3S2Nhwc._cell_weight(wb, taps, transpose=True)
+      if off == 0:
+        torch.mm(dO[base:], wc_t, out=dX[base:])
+      else:
+        dX[base + off:Rp + off, k0:k1].addmm_(dO[base:], wc_t)
+    return dX.reshape(B, Hp, Wp, 4 * C), dw, db.to(ctx.bias_dtype)
+
+
 class ConvSubsampling(BaseLayer):
   """2x Conv2D stride-2 frontend: [B, T, F] mel -> [B, T/4, D]
   (reference tasks/asr/encoder conv subsampling). conv1 (Cin=1, K=9) is
   a small unfold+GEMM; conv2 (Cin=Cout=C) runs the offset-GEMM
-  _Conv3x3S2Nhwc path."""
+  _Conv3x3S2Nhwc path. With py_utils.GlueFusion() on GPU bf16
+  (channels % 8 == 0, features without grad) conv1 + ReLU write conv2's
+  s2d buffer directly and conv2's output side is fused (_Conv1S2d,
+  _Conv3x3S2ReluFromS2d)."""
 
   @classmethod
   def Params(cls):
@@ -414,17 +514,27 @@ class ConvSubsampling(BaseLayer):
     """inputs [B, T, F] -> (out [B, ceil(T/4), D], out_paddings)."""
     b, t, f = inputs.shape
     ch = self._ch
-    # conv1 (Cin=1): unfold + GEMM, output NHWC directly. cols are tiny
-    # (9 x T*F/4 per example).
-    cols = F.unfold(inputs.unsqueeze(1), kernel_size=3, stride=2,
-                    padding=1)  # [B, 9, HW]
-    h1 = (f + 1) // 2
-    t1 = (t + 1) // 2
-    x = torch.matmul(cols.transpose(1, 2),
-                     theta.conv1_w.reshape(9, ch)) + theta.conv1_b
-    x = F.relu(x).reshape(b, t1, h1, ch)  # NHWC
-    # conv2: offset-GEMM path (no cols buffer).
-    x = F.relu(_Conv3x3S2Nhwc.apply(x, theta.conv2_w, theta.conv2_b))
+    if (py_utils.GlueFusion() and inputs.is_cuda and b > 0 and
+        ch % 8 == 0 and not inputs.requires_grad and
+        all(v.dtype == torch.bfloat16 for v in (
+            inputs, theta.conv1_w, theta.conv1_b, theta.conv2_w,
+            theta.conv2_b))):
+      # conv1 + ReLU land in conv2's s2d buffer; conv2's bias, slice, ReLU
+      # and their backward are fused around the same four cell GEMMs.
+      X = _Conv1S2d.apply(inputs.contiguous(), theta.conv1_w, theta.conv1_b)
+      x = _Conv3x3S2ReluFromS2d.apply(X, theta.conv2_w, theta.conv2_b)
+    else:
+      # conv1 (Cin=1): unfold + GEMM, output NHWC directly. cols are tiny
+      # (9 x T*F/4 per example).
+      cols = F.unfold(inputs.unsqueeze(1), kernel_size=3, stride=2,
+                      padding=1)  # [B, 9, HW]
+      h1 = (f + 1) // 2
+      t1 = (t + 1) // 2
+      x = torch.matmul(cols.transpose(1, 2),
+                       theta.conv1_w.reshape(9, ch)) + theta.conv1_b
+      x = F.relu(x).reshape(b, t1, h1, ch)  # NHWC
+      # conv2: offset-GEMM path (no cols buffer).
+      x = F.relu(_Conv3x3S2Nhwc.apply(x, theta.conv2_w, theta.conv2_b))
     _, t4, f4, _ = x.shape
     x = x.reshape(b, t4, f4 * ch)
     out = torch.addmm(theta.proj_b, x.reshape(-1, f4 * ch),

@@ -140,6 +140,14 @@ std::vector<torch::Tensor> moe_positions(torch::Tensor top1,
 torch::Tensor s2d_fwd(torch::Tensor x);
 torch::Tensor s2d_inv(torch::Tensor dX, int64_t C);
 torch::Tensor pad_scatter(torch::Tensor dout);
+torch::Tensor conv1_s2d_fwd(torch::Tensor x, torch::Tensor w1,
+                            torch::Tensor b1, int64_t max_blocks);
+std::vector<torch::Tensor> conv1_s2d_bwd(torch::Tensor dX, torch::Tensor X,
+                                         torch::Tensor x, int64_t max_blocks);
+torch::Tensor unpad_relu(torch::Tensor O);
+std::vector<torch::Tensor> pad_scatter_relu_bwd(torch::Tensor dout,
+                                                torch::Tensor y,
+                                                int64_t max_blocks);
 
 // topk.hip
 std::vector<torch::Tensor> topk_rows(torch::Tensor scores, int64_t k);
@@ -331,4 +339,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk_rows", &topk_rows, "Row-wise top-k (beam pruning, K12)");
   m.def("s2d_inv", &s2d_inv, "Inverse space-to-depth");
   m.def("pad_scatter", &pad_scatter, "Zero-border pad scatter");
+  m.def("conv1_s2d_fwd", &conv1_s2d_fwd,
+        "relu(conv1(x) + b1) (Cin=1, 3x3/s2) written in padded s2d layout",
+        py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("max_blocks") = 0);
+  m.def("conv1_s2d_bwd", &conv1_s2d_bwd,
+        "conv1 weight and bias gradients (fp32) from dX and X in s2d layout",
+        py::arg("dX"), py::arg("X"), py::arg("x"), py::arg("max_blocks") = 0);
+  m.def("unpad_relu", &unpad_relu, "relu(O[:, 1:, 1:, :]), contiguous");
+  m.def("pad_scatter_relu_bwd", &pad_scatter_relu_bwd,
+        "Zero-border pad of dout * (y > 0) plus its fp32 column sums",
+        py::arg("dout"), py::arg("y"), py::arg("max_blocks") = 0);
 }
