@@ -178,6 +178,21 @@ int64_t attend_denc_row_tile();
 int64_t attend_lds_limit();
 int64_t attend_lds_bytes(int64_t s, int64_t d, bool bwd);
 
+// las_step.hip
+void las_step_fwd(c10::optional<torch::Tensor> a1,
+                  c10::optional<torch::Tensor> a2, torch::Tensor wt,
+                  torch::Tensor pre, c10::optional<torch::Tensor> c_prev,
+                  torch::Tensor gates, torch::Tensor c_out,
+                  torch::Tensor m_out, double fgb, double cap,
+                  int64_t rows_per_block);
+void las_cell_bwd(torch::Tensor a, torch::Tensor wt,
+                  c10::optional<torch::Tensor> add_b,
+                  c10::optional<torch::Tensor> add_f, torch::Tensor gates,
+                  c10::optional<torch::Tensor> c_prev, torch::Tensor dc_carry,
+                  bool has_dc, torch::Tensor dgates,
+                  c10::optional<torch::Tensor> pass_out, double fgb,
+                  double cap, int64_t rows_per_block);
+
 // lstm_scan.hip
 void lstm_scan_fwd(torch::Tensor gates, torch::Tensor c, torch::Tensor m,
                    torch::Tensor pad, torch::Tensor wmt, int64_t rev_mask,
@@ -311,6 +326,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Dynamic LDS bytes an attend_* launch may ask for on this device");
   m.def("attend_lds_bytes", &attend_lds_bytes,
         "Dynamic LDS bytes attend_fwd/attend_bwd ask for at (S, D)");
+  m.def("las_step_fwd", &las_step_fwd,
+        "Decoder LSTM stage fwd: two-source step GEMM with the cell as "
+        "epilogue, into caller rows (gates, c, m)",
+        py::arg("a1"), py::arg("a2"), py::arg("wt"), py::arg("pre"),
+        py::arg("c_prev"), py::arg("gates"), py::arg("c_out"),
+        py::arg("m_out"), py::arg("fgb"), py::arg("cap"),
+        py::arg("rows_per_block") = 0);
+  m.def("las_cell_bwd", &las_cell_bwd,
+        "Decoder LSTM cell bwd with its data-gradient GEMM as prologue "
+        "(dgates out, fp32 dc_carry in place, optional fp32 pass_out half)",
+        py::arg("a"), py::arg("wt"), py::arg("add_b"), py::arg("add_f"),
+        py::arg("gates"), py::arg("c_prev"), py::arg("dc_carry"),
+        py::arg("has_dc"), py::arg("dgates"), py::arg("pass_out"),
+        py::arg("fgb"), py::arg("cap"), py::arg("rows_per_block") = 0);
   m.def("lstm_scan_fwd", &lstm_scan_fwd,
         "Fused LSTM scan forward: one launch per step, all directions");
   m.def("lstm_scan_bwd", &lstm_scan_bwd,

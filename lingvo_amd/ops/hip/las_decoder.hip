@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "mfma.h"
+#include "tile_gemm.h"
 
 namespace {
 
@@ -33,15 +34,17 @@ namespace {
 // smallm_gemm: out[M,N] = alpha * (A[M,K] @ Wt[N,K]^T) + pre
 //   pre_mode: 0 none, 1 row-vector [N], 2 full matrix [M,N],
 //             3 accumulate into existing out
-// A row-major [M, K] (contiguous), Wt row-major [N, ldw] with the
-// mathematical W^T in its first K columns. K % 32 == 0.
+// A row-major [M, K] with row stride lda (a column slice of a wider
+// matrix is fine), Wt row-major [N, ldw] with the mathematical W^T in its
+// first K columns. K % 32 == 0.
 // Grid: (ceil(N/16), ceil(M/128)); block 256 = 4 waves; wave w owns a
-// quarter of K for all 8 m-tiles of its 128-row m-block.
+// quarter of K for all 8 m-tiles of its 128-row m-block and walks it with
+// the shared K loop of tile_gemm.h.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void smallm_gemm_kernel(
     const unsigned short* __restrict__ a, const unsigned short* __restrict__ wt,
     const unsigned short* __restrict__ pre, unsigned short* __restrict__ out,
-    int m, int n, int k, long ldw, float alpha, int pre_mode) {
+    int m, int n, int k, long lda, long ldw, float alpha, int pre_mode) {
   // K-SPLIT layout: every wave computes ALL 8 m-tiles over its quarter
   // of K (no per-iteration block syncs; the serial K chain is 4x
   // shorter than an M-split), then waves 1-3 spill partials to LDS and
@@ -68,27 +71,17 @@ __global__ __launch_bounds__(256) void smallm_gemm_kernel(
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
 
-  for (int k0 = k_lo; k0 < k_hi; k0 += 32) {
-    bf16x8 bf;
-    if (col_ok) {
-      bf = load_bf16x8_bits(wt + (long)col * ldw + k0 + g * 8);
-    } else {
-      float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      bf = pack_bf16x8(z);
-    }
+  // Rows beyond M and columns beyond N re-read the last valid one instead
+  // of branching to a zero fragment: an output element depends on its own
+  // A row and Wt row alone, and those elements are never stored.
+  const unsigned short* brow =
+      wt + (long)min(col, n - 1) * ldw + k_lo + g * 8;
+  const unsigned short* arow[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int row = m0 + mt * 16 + cl;
-      bf16x8 af;
-      if (row < m) {
-        af = load_bf16x8_bits(a + (long)row * k + k0 + g * 8);
-      } else {
-        float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        af = pack_bf16x8(z);
-      }
-      acc[mt] = mfma16x16x32_bf16(af, bf, acc[mt]);
-    }
+  for (int mt = 0; mt < MT; ++mt) {
+    arow[mt] = a + (long)min(m0 + mt * 16 + cl, m - 1) * lda + k_lo + g * 8;
   }
+  tile_gemm<MT>(arow, brow, k_hi - k_lo, acc);
 
   // Cross-wave reduction: C layout row = mt*16 + g*4 + r, col = cl.
   if (wid > 0) {
@@ -831,8 +824,15 @@ void smallm_gemm(torch::Tensor a, torch::Tensor wt,
                  c10::optional<torch::Tensor> pre, torch::Tensor out,
                  int64_t k, int64_t wt_col0, double alpha,
                  int64_t pre_mode) {
-  TORCH_CHECK(cuda_contig(a, torch::kBFloat16) && a.dim() == 2,
-              "a must be CUDA contiguous bf16 [M,K]");
+  // a may be a column slice of a wider matrix: unit column stride, rows
+  // and base 16-byte aligned for the bf16x8 fragment loads.
+  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 &&
+              a.dim() == 2 && (a.size(1) == 1 || a.stride(1) == 1) &&
+              (a.size(0) == 1 || (a.stride(0) >= a.size(1) &&
+                                  a.stride(0) % 8 == 0)) &&
+              (uintptr_t)a.data_ptr() % 16 == 0,
+              "a must be CUDA bf16 [M,K] with unit column stride and "
+              "16-byte aligned rows");
   TORCH_CHECK(cuda_contig(wt, torch::kBFloat16) && wt.dim() == 2,
               "wt must be CUDA contiguous bf16 [>=N,ldw]");
   TORCH_CHECK(cuda_contig(out, torch::kBFloat16) && out.dim() == 2,
@@ -869,7 +869,8 @@ void smallm_gemm(torch::Tensor a, torch::Tensor wt,
                      stream, (const unsigned short*)a.data_ptr(),
                      (const unsigned short*)wt.data_ptr() + wt_col0,
                      prep, (unsigned short*)out.data_ptr(), m, n, (int)k,
-                     ldw, (float)alpha, (int)pre_mode);
+                     m == 1 ? (long)k : (long)a.stride(0), ldw, (float)alpha,
+                     (int)pre_mode);
   LV_CHECK_HIP(hipGetLastError());
 }
 

@@ -27,59 +27,22 @@
 // step pays one round of load latency, not two.
 //
 // A step is latency-bound (the next launch depends on it), so the K loop
-// is written for loads in flight, not for occupancy: no per-row branches
-// (rows beyond B re-read row B-1: output row r of an MFMA depends on A
-// row r alone, and the pointwise part never stores those rows) and KU
-// k-steps of fragments loaded ahead of their MFMAs.
+// (tile_gemm.h) is written for loads in flight, not for occupancy: no
+// per-row branches (rows beyond B re-read row B-1: output row r of an MFMA
+// depends on A row r alone, and the pointwise part never stores those
+// rows) and KU k-steps of fragments loaded ahead of their MFMAs.
 
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
 
 #include "common.h"
 #include "mfma.h"
+#include "tile_gemm.h"
 
 namespace {
 
 __device__ __forceinline__ float sigf(float x) {
   return 1.f / (1.f + __expf(-x));
-}
-
-// acc[mt] += A_mt[16, k_len] @ B[16, k_len]^T with per-lane fragment
-// pointers (arow[mt] / brow already include the lane's row and k-group
-// offset). k_len % 32 == 0.
-template <int MT>
-__device__ __forceinline__ void tile_gemm(
-    const unsigned short* const (&arow)[MT], const unsigned short* brow,
-    int k_len, f32x4 (&acc)[MT]) {
-  constexpr int KU = MT == 1 ? 8 : (MT == 2 ? 4 : 2);  // k-steps in flight
-  int k0 = 0;
-  for (; k0 + 32 * KU <= k_len; k0 += 32 * KU) {
-    bf16x8 bf[KU];
-    bf16x8 af[KU][MT];
-#pragma unroll
-    for (int u = 0; u < KU; ++u) {
-      bf[u] = load_bf16x8_bits(brow + k0 + u * 32);
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        af[u][mt] = load_bf16x8_bits(arow[mt] + k0 + u * 32);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < KU; ++u) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        acc[mt] = mfma16x16x32_bf16(af[u][mt], bf[u], acc[mt]);
-      }
-    }
-  }
-  for (; k0 < k_len; k0 += 32) {
-    const bf16x8 bf = load_bf16x8_bits(brow + k0);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      acc[mt] = mfma16x16x32_bf16(load_bf16x8_bits(arow[mt] + k0), bf,
-                                  acc[mt]);
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------

@@ -21,6 +21,14 @@ Two routes for the attention step (attend_route):
     (attend_denc), written once in enc's dtype.
   - 'accumulate': attend_fwd / attend_bwd, which add every step's dEnc
     increment into an fp32 [B,S,D] buffer.
+
+Two routes for the LSTM stages (step_route):
+  - 'fused' (the default, 'auto', where the shapes qualify): las_step_fwd
+    runs a layer's two GEMM halves, its bias / embedding term and the cell
+    as one launch into rows of [L,B,*] stacks; las_cell_bwd runs the cell
+    backward with its data-gradient GEMM as prologue and fp32 carries. A
+    step is 4 launches forward and 4 backward.
+  - 'split': one op per GEMM, cell, add and copy (8 + 12 launches).
 """
 
 from __future__ import annotations
@@ -33,11 +41,45 @@ import torch
 from lingvo_amd.ops import _loader
 
 
+def _fused_bwd_sweep(ext, dctx_parts, dm1_parts, probs, ctx32s, enc_b, scale,
+                     gates0, gates1, c0s, c1s, wq_b, wm1_b, w_cm0_b, dcm,
+                     src_dim, fgb, cap, dctx_st, dl_st, dqs, dgates0,
+                     dgates1):
+  """Reverse sweep of the 'fused' step route: four launches per step.
+
+  The dc carries and the dm1 carry live in fp32 [B,H] scratch that the
+  kernels update; the step processed first takes "no carry" as a flag, not
+  a zero fill. dcm's two halves are read in place as strided views."""
+  L, B, G4 = gates0.shape
+  H = G4 // 4
+  f32 = dict(dtype=torch.float32, device=gates0.device)
+  dc0 = torch.empty(B, H, **f32)
+  dc1 = torch.empty(B, H, **f32)
+  dm1_carry = torch.empty(B, H, **f32)
+  dctx_carry, dm0_carry = dcm[:, :src_dim], dcm[:, src_dim:]
+  for t in range(L - 1, -1, -1):
+    carry = t < L - 1
+    ext.attend_step_bwd(dctx_parts[t], dctx_carry if carry else None,
+                        probs[t], ctx32s[t], enc_b, scale, dctx_st[t],
+                        dl_st[t], dqs[t])
+    # dgates1[t] from dm1 = dq @ wq^T + out grad + carry.
+    ext.las_cell_bwd(dqs[t], wq_b, dm1_parts[t],
+                     dm1_carry if carry else None, gates1[t],
+                     c1s[t - 1] if t > 0 else None, dc1, carry, dgates1[t],
+                     None, fgb, cap)
+    # dgates1[t] @ wm1^T: columns < H are dm0 (-> dgates0[t]), the rest is
+    # the next dm1 carry.
+    ext.las_cell_bwd(dgates1[t], wm1_b, dm0_carry if carry else None, None,
+                     gates0[t], c0s[t - 1] if t > 0 else None, dc0, carry,
+                     dgates0[t], dm1_carry, fgb, cap)
+    ext.smallm_gemm(dgates0[t], w_cm0_b, None, dcm, G4, 0, 1.0, 0)
+
+
 class _DecoderRecurrenceFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, emb_gates, w_cm0, b1, wm1, wq, enc, enc_pad, fgb, cap,
-              src_dim, deferred):
+              src_dim, deferred, fused):
     ext = _loader.get_ext(required=True)
     B, L, G4 = emb_gates.shape
     H = G4 // 4
@@ -67,6 +109,32 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
       ctx_st = torch.empty(L, B, D, dtype=dt, device=dev)
       ctx32_st = torch.empty(L, B, D, dtype=torch.float32, device=dev)
       probs_st = torch.empty(L, B, S, dtype=torch.float32, device=dev)
+    if fused:
+      # One launch per LSTM layer: both GEMM halves, the bias / embedding
+      # term and the cell, written into rows of the [L,B,H] stacks. The
+      # first step skips the K ranges of the missing previous state.
+      c0_st = torch.empty(L, B, H, dtype=dt, device=dev)
+      m0_st = torch.empty(L, B, H, dtype=dt, device=dev)
+      c1_st = torch.empty(L, B, H, dtype=dt, device=dev)
+      m1_st = torch.empty(L, B, H, dtype=dt, device=dev)
+      prev_row = lambda st, t: st[t - 1] if t > 0 else None
+      for t in range(L):
+        prev = lambda st: prev_row(st, t)
+        ext.las_step_fwd(prev(ctx_st), prev(m0_st), w1t, eg_t[t],
+                         prev(c0_st), gates0[t], c0_st[t], m0_st[t], fgb,
+                         cap)
+        ext.las_step_fwd(m0_st[t], prev(m1_st), wm1t, b1_b, prev(c1_st),
+                         gates1[t], c1_st[t], m1_st[t], fgb, cap)
+        ext.smallm_gemm(m1_st[t], wqt, None, qs[t], H, 0, 1.0, 0)
+        ext.attend_step_fwd(qs[t], enc_b, pad_f, scale, probs_st[t],
+                            ctx_st[t], ctx32_st[t])
+      ctx.save_for_backward(
+          emb_gates_b, w_cm0, wm1, wq, enc_b, pad_f, gates0, gates1, qs,
+          c0_st, m0_st, c1_st, m1_st, ctx_st, probs_st, ctx32_st)
+      ctx.cfg = (fgb, cap, src_dim, scale, b1.dtype, enc.dtype,
+                 emb_gates.dtype, deferred, fused)
+      return torch.cat(
+          [m1_st.permute(1, 0, 2), ctx_st.permute(1, 0, 2)], dim=-1)
     for t in range(L):
       g0 = gates0[t]
       ext.smallm_gemm(ctxv, w1t, eg_t[t], g0, src_dim, 0, 1.0, 2)
@@ -101,7 +169,7 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
         torch.stack(c0s), torch.stack(m0s), torch.stack(c1s), m1_st,
         ctx_st, probs_st, ctx32_st)
     ctx.cfg = (fgb, cap, src_dim, scale, b1.dtype, enc.dtype,
-               emb_gates.dtype, deferred)
+               emb_gates.dtype, deferred, fused)
     out = torch.cat(
         [m1_st.permute(1, 0, 2), ctx_st.permute(1, 0, 2)], dim=-1)
     return out  # [B, L, H + D]
@@ -112,7 +180,7 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
     (emb_gates_b, w_cm0, wm1, wq, enc_b, pad_f, gates0, gates1, qs, c0s,
      m0s, c1s, m1s, ctxs, probs, ctx32s) = ctx.saved_tensors
     (fgb, cap, src_dim, scale, b1_dtype, enc_dtype, eg_dtype,
-     deferred) = ctx.cfg
+     deferred, fused) = ctx.cfg
     L, B, G4 = gates0.shape
     H = G4 // 4
     D = qs.shape[-1]
@@ -146,7 +214,13 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
     dout_t = dout.permute(1, 0, 2)
     dm1_parts = dout_t[:, :, :H].contiguous()   # [L, B, H]
     dctx_parts = dout_t[:, :, H:].contiguous()  # [L, B, D]
-    for t in range(L - 1, -1, -1):
+    if fused:
+      _fused_bwd_sweep(ext, dctx_parts, dm1_parts, probs, ctx32s, enc_b,
+                       scale, gates0, gates1, c0s, c1s, wq_b, wm1_b, w_cm0_b,
+                       dcm, src_dim, fgb, cap, dctx_st, dl_st, dqs, dgates0,
+                       dgates1)
+    # 'split': the op-per-stage sweep.
+    for t in (range(0) if fused else range(L - 1, -1, -1)):
       if deferred:
         dq = dqs[t]
         ext.attend_step_bwd(dctx_parts[t], dctx_carry, probs[t], ctx32s[t],
@@ -197,7 +271,7 @@ class _DecoderRecurrenceFn(torch.autograd.Function):
           dtype=dt if enc_dtype == torch.bfloat16 else torch.float32)
       ext.attend_denc(dl_st, probs, qs, dctx_st, denc)
     return (demb_gates, dw_cm0, db1, dwm1, dwq, denc.to(enc_dtype),
-            None, None, None, None, None)
+            None, None, None, None, None, None)
 
 
 def decoder_recurrence(emb_gates: torch.Tensor, w_cm0: torch.Tensor,
@@ -205,7 +279,8 @@ def decoder_recurrence(emb_gates: torch.Tensor, w_cm0: torch.Tensor,
                        wq: torch.Tensor, enc: torch.Tensor,
                        enc_pad: torch.Tensor, fgb: float, cap: float,
                        src_dim: int,
-                       attend_route: str = 'auto') -> torch.Tensor:
+                       attend_route: str = 'auto',
+                       step_route: str = 'auto') -> torch.Tensor:
   """Teacher-forced 2-layer LSTM + dot-attention decoder over L steps.
 
   emb_gates [B,L,4H]: per-step precomputed gate contribution of the
@@ -215,9 +290,26 @@ def decoder_recurrence(emb_gates: torch.Tensor, w_cm0: torch.Tensor,
 
   attend_route: 'deferred' reads enc once per step and forms dEnc in one
   kernel after the loop; 'accumulate' adds every step's increment into an
-  fp32 dEnc buffer; 'auto' is 'deferred'."""
+  fp32 dEnc buffer; 'auto' is 'deferred'.
+
+  step_route: 'fused' runs each LSTM layer of a step as one launch (both
+  GEMM halves and the cell, las_step.hip) and the backward cell stages with
+  their data-gradient GEMMs as prologue, with fp32 carries; 'split' is one
+  op per GEMM, cell and add. 'fused' needs the deferred attention route and
+  H % 32 == 0, src_dim % 32 == 0 (every K range a multiple of the MFMA
+  k-step); 'auto' picks it where those hold and 'split' elsewhere."""
   if attend_route not in ('auto', 'deferred', 'accumulate'):
     raise ValueError(f'unknown attend_route {attend_route!r}')
+  if step_route not in ('auto', 'fused', 'split'):
+    raise ValueError(f'unknown step_route {step_route!r}')
+  deferred = attend_route != 'accumulate'
+  H = emb_gates.shape[-1] // 4
+  fused_ok = deferred and H % 32 == 0 and src_dim % 32 == 0
+  if step_route == 'fused' and not fused_ok:
+    raise ValueError(
+        "step_route='fused' needs the deferred attend_route and "
+        f'H % 32 == 0, src_dim % 32 == 0 (H={H}, src_dim={src_dim})')
+  fused = fused_ok and step_route != 'split'
   return _DecoderRecurrenceFn.apply(emb_gates, w_cm0, b1, wm1, wq, enc,
-                                    enc_pad, fgb, cap, src_dim,
-                                    attend_route != 'accumulate')
+                                    enc_pad, fgb, cap, src_dim, deferred,
+                                    fused)
