@@ -25,6 +25,7 @@
 #include <climits>
 
 #include "common.h"
+#include "host_checks.h"
 #include "mfma.h"
 #include "tile_gemm.h"
 
@@ -53,10 +54,8 @@ __global__ __launch_bounds__(256) void smallm_gemm_kernel(
   const int nt = blockIdx.x;          // n-tile (16 cols)
   const int col0 = nt * 16;
   const int m0 = blockIdx.y * 128;    // m-block (rows handled here)
-  const int wid = threadIdx.x / WAVE_SIZE;
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4;            // k-group 0..3
-  const int cl = lane & 15;           // row-in-frag / col-in-frag
+  const StepThread th = step_thread();
+  const int wid = th.wid, g = th.g, cl = th.cl;
   const int col = col0 + cl;
   const bool col_ok = col < n;
 
@@ -84,15 +83,7 @@ __global__ __launch_bounds__(256) void smallm_gemm_kernel(
   tile_gemm<MT>(arow, brow, k_hi - k_lo, acc);
 
   // Cross-wave reduction: C layout row = mt*16 + g*4 + r, col = cl.
-  if (wid > 0) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[wid - 1][mt * 16 + g * 4 + r][cl] = acc[mt][r];
-      }
-    }
-  }
+  if (wid > 0) park_acc<MT>(red[wid - 1], g, cl, acc);
   __syncthreads();
   if (wid != 0) return;
 #pragma unroll
@@ -800,10 +791,6 @@ size_t attend_bwd_lds(int64_t s, int64_t d) {
   return (size_t)d * 4 + (size_t)s * 4 + (size_t)4 * d * 4 + 16;
 }
 
-bool cuda_contig(const torch::Tensor& t, torch::ScalarType st) {
-  return t.is_cuda() && t.is_contiguous() && t.scalar_type() == st;
-}
-
 // Checks shared by attend_fwd (q, enc, pad) and attend_bwd (q, enc).
 void check_attend_q_enc(const torch::Tensor& q, const torch::Tensor& enc) {
   TORCH_CHECK(cuda_contig(q, torch::kBFloat16) && q.dim() == 2,
@@ -829,8 +816,7 @@ void smallm_gemm(torch::Tensor a, torch::Tensor wt,
   TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 &&
               a.dim() == 2 && (a.size(1) == 1 || a.stride(1) == 1) &&
               (a.size(0) == 1 || (a.stride(0) >= a.size(1) &&
-                                  a.stride(0) % 8 == 0)) &&
-              (uintptr_t)a.data_ptr() % 16 == 0,
+                                  a.stride(0) % 8 == 0)) && aligned16(a),
               "a must be CUDA bf16 [M,K] with unit column stride and "
               "16-byte aligned rows");
   TORCH_CHECK(cuda_contig(wt, torch::kBFloat16) && wt.dim() == 2,
@@ -866,11 +852,9 @@ void smallm_gemm(torch::Tensor a, torch::Tensor wt,
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(smallm_gemm_kernel,
                      dim3(cdiv(n, 16), cdiv(m, 128)), dim3(256), 0,
-                     stream, (const unsigned short*)a.data_ptr(),
-                     (const unsigned short*)wt.data_ptr() + wt_col0,
-                     prep, (unsigned short*)out.data_ptr(), m, n, (int)k,
-                     m == 1 ? (long)k : (long)a.stride(0), ldw, (float)alpha,
-                     (int)pre_mode);
+                     stream, u16(a), u16(wt) + wt_col0, prep, u16(out), m, n,
+                     (int)k, m == 1 ? (long)k : (long)a.stride(0), ldw,
+                     (float)alpha, (int)pre_mode);
   LV_CHECK_HIP(hipGetLastError());
 }
 
@@ -879,8 +863,7 @@ std::vector<torch::Tensor> attend_fwd(torch::Tensor q, torch::Tensor enc,
   check_attend_q_enc(q, enc);
   const int b = q.size(0), d = q.size(1);
   const int s = enc.size(1);
-  TORCH_CHECK(cuda_contig(pad, torch::kFloat32) && pad.dim() == 2 &&
-              pad.size(0) == b && pad.size(1) == s,
+  TORCH_CHECK(cuda_rows(pad, torch::kFloat32, b, s),
               "pad must be CUDA contiguous fp32 [B,S]");
   const size_t shmem = attend_fwd_lds(s, d);
   TORCH_CHECK(shmem <= lds_limit_bytes(), "attend_fwd: S=", s, " D=", d,
@@ -889,11 +872,8 @@ std::vector<torch::Tensor> attend_fwd(torch::Tensor q, torch::Tensor enc,
   auto ctx = torch::empty({b, d}, q.options());
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(attend_fwd_kernel, dim3(b), dim3(256), shmem, stream,
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)enc.data_ptr(),
-                     pad.data_ptr<float>(), probs.data_ptr<float>(),
-                     (unsigned short*)ctx.data_ptr(), b, s, d,
-                     (float)scale);
+                     u16(q), u16(enc), pad.data_ptr<float>(),
+                     probs.data_ptr<float>(), u16(ctx), b, s, d, (float)scale);
   LV_CHECK_HIP(hipGetLastError());
   return {probs, ctx};
 }
@@ -909,8 +889,7 @@ std::vector<torch::Tensor> attend_bwd(torch::Tensor dctx,
   TORCH_CHECK(dctx.is_cuda() && dctx.is_floating_point() &&
               dctx.dim() == 2 && dctx.size(0) == b && dctx.size(1) == d,
               "dctx must be a CUDA float tensor [B,D]");
-  TORCH_CHECK(cuda_contig(probs, torch::kFloat32) && probs.dim() == 2 &&
-              probs.size(0) == b && probs.size(1) == s,
+  TORCH_CHECK(cuda_rows(probs, torch::kFloat32, b, s),
               "probs must be CUDA contiguous fp32 [B,S]");
   TORCH_CHECK(cuda_contig(denc, torch::kFloat32) && denc.dim() == 3 &&
               denc.size(0) == b && denc.size(1) == s && denc.size(2) == d,
@@ -922,12 +901,8 @@ std::vector<torch::Tensor> attend_bwd(torch::Tensor dctx,
   auto dq = torch::empty({b, d}, q.options());
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(attend_bwd_kernel, dim3(b), dim3(256), shmem, stream,
-                     (const unsigned short*)dctx_c.data_ptr(),
-                     probs.data_ptr<float>(),
-                     (const unsigned short*)q.data_ptr(),
-                     (const unsigned short*)enc.data_ptr(),
-                     (unsigned short*)dq.data_ptr(),
-                     denc.data_ptr<float>(), b, s, d, (float)scale);
+                     u16(dctx_c), probs.data_ptr<float>(), u16(q), u16(enc),
+                     u16(dq), denc.data_ptr<float>(), b, s, d, (float)scale);
   LV_CHECK_HIP(hipGetLastError());
   return {dq};
 }
@@ -967,14 +942,6 @@ size_t attend_step_bwd_lds(int64_t s, int64_t d, int nw) {
   return (size_t)d * 4 + (size_t)nw * d * 4 + (size_t)nw * 4;
 }
 
-// A [rows, cols] tensor of dtype st whose rows are dense (a row of a
-// larger contiguous stack is).
-bool cuda_rows(const torch::Tensor& t, torch::ScalarType st, int64_t rows,
-               int64_t cols) {
-  return t.is_cuda() && t.scalar_type() == st && t.dim() == 2 &&
-         t.size(0) == rows && t.size(1) == cols && t.is_contiguous();
-}
-
 #define LV_STEP_CASE(NDV, U, NW, KERNEL, ...)                               \
   if (ndv == NDV && u == U && nw == NW) {                                   \
     hipLaunchKernelGGL((KERNEL<NDV, U, NW>), dim3(b), dim3(NW * WAVE_SIZE), \
@@ -1005,8 +972,7 @@ void attend_step_fwd(torch::Tensor q, torch::Tensor enc, torch::Tensor pad,
   check_attend_q_enc(q, enc);
   const int b = q.size(0), d = q.size(1);
   const int s = enc.size(1);
-  TORCH_CHECK(cuda_contig(pad, torch::kFloat32) && pad.dim() == 2 &&
-              pad.size(0) == b && pad.size(1) == s,
+  TORCH_CHECK(cuda_rows(pad, torch::kFloat32, b, s),
               "pad must be CUDA contiguous fp32 [B,S]");
   TORCH_CHECK(cuda_rows(probs, torch::kFloat32, b, s),
               "probs must be CUDA contiguous fp32 [B,S]");
@@ -1022,12 +988,9 @@ void attend_step_fwd(torch::Tensor q, torch::Tensor enc, torch::Tensor pad,
               " needs ", shmem, " bytes of LDS, over the device limit");
   const int ndv = cdiv(d, WAVE_SIZE * 8);
   auto stream = at::cuda::getCurrentCUDAStream();
-  LV_STEP_DISPATCH(attend_step_fwd_kernel,
-                   (const unsigned short*)q.data_ptr(),
-                   (const unsigned short*)enc.data_ptr(),
-                   pad.data_ptr<float>(), probs.data_ptr<float>(),
-                   (unsigned short*)ctx.data_ptr(), ctx32.data_ptr<float>(),
-                   s, d, (float)scale)
+  LV_STEP_DISPATCH(attend_step_fwd_kernel, u16(q), u16(enc),
+                   pad.data_ptr<float>(), probs.data_ptr<float>(), u16(ctx),
+                   ctx32.data_ptr<float>(), s, d, (float)scale)
   LV_CHECK_HIP(hipGetLastError());
 }
 
@@ -1041,13 +1004,8 @@ void attend_step_bwd(torch::Tensor dctx_a, c10::optional<torch::Tensor> dctx_b,
   const unsigned short* bp = nullptr;
   long ldb = 0;
   if (dctx_b.has_value()) {
-    const torch::Tensor& t = *dctx_b;
-    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
-                t.dim() == 2 && t.size(0) == b && t.size(1) == d &&
-                t.stride(1) == 1 && t.stride(0) >= d,
-                "dctx_b must be CUDA bf16 [B,D] with unit column stride");
-    bp = (const unsigned short*)t.data_ptr();
-    ldb = t.stride(0);
+    ldb = check_strided_rows(*dctx_b, b, d, "dctx_b");
+    bp = (const unsigned short*)dctx_b->data_ptr();
   }
   TORCH_CHECK(cuda_rows(probs, torch::kFloat32, b, s),
               "probs must be CUDA contiguous fp32 [B,S]");
@@ -1067,13 +1025,10 @@ void attend_step_bwd(torch::Tensor dctx_a, c10::optional<torch::Tensor> dctx_b,
               " needs ", shmem, " bytes of LDS, over the device limit");
   const int ndv = cdiv(d, WAVE_SIZE * 8);
   auto stream = at::cuda::getCurrentCUDAStream();
-  LV_STEP_DISPATCH(attend_step_bwd_kernel,
-                   (const unsigned short*)dctx_a.data_ptr(), bp, ldb,
-                   probs.data_ptr<float>(), ctx32.data_ptr<float>(),
-                   (const unsigned short*)enc.data_ptr(),
-                   (unsigned short*)dctx_out.data_ptr(),
-                   dl.data_ptr<float>(), (unsigned short*)dq.data_ptr(), s,
-                   d, (float)scale)
+  LV_STEP_DISPATCH(attend_step_bwd_kernel, u16(dctx_a), bp, ldb,
+                   probs.data_ptr<float>(), ctx32.data_ptr<float>(), u16(enc),
+                   u16(dctx_out), dl.data_ptr<float>(), u16(dq), s, d,
+                   (float)scale)
   LV_CHECK_HIP(hipGetLastError());
 }
 
@@ -1107,18 +1062,14 @@ void attend_denc(torch::Tensor dl, torch::Tensor probs, torch::Tensor qs,
   auto stream = at::cuda::getCurrentCUDAStream();
   if (out.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL(attend_denc_kernel<float>, grid, dim3(256), 0, stream,
-                       dl.data_ptr<float>(), probs.data_ptr<float>(),
-                       (const unsigned short*)qs.data_ptr(),
-                       (const unsigned short*)dctx.data_ptr(),
-                       out.data_ptr<float>(), (int)l, (int)b, (int)s, (int)d,
-                       (int)s_tiles);
+                       dl.data_ptr<float>(), probs.data_ptr<float>(), u16(qs),
+                       u16(dctx), out.data_ptr<float>(), (int)l, (int)b,
+                       (int)s, (int)d, (int)s_tiles);
   } else {
     hipLaunchKernelGGL(attend_denc_kernel<unsigned short>, grid, dim3(256), 0,
                        stream, dl.data_ptr<float>(), probs.data_ptr<float>(),
-                       (const unsigned short*)qs.data_ptr(),
-                       (const unsigned short*)dctx.data_ptr(),
-                       (unsigned short*)out.data_ptr(), (int)l, (int)b,
-                       (int)s, (int)d, (int)s_tiles);
+                       u16(qs), u16(dctx), u16(out), (int)l, (int)b, (int)s,
+                       (int)d, (int)s_tiles);
   }
   LV_CHECK_HIP(hipGetLastError());
 }

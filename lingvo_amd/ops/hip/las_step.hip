@@ -1,10 +1,11 @@
 // Fused LAS decoder recurrence stages for gfx950: the step GEMMs of the
 // teacher-forced decoder (ops/las_decoder.py) with the LSTM cell and the
-// glue around it as their epilogue, after the design of lstm_scan.hip.
+// glue around it as their epilogue, on the step-kernel skeleton of
+// tile_gemm.h that lstm_scan.hip uses too.
 //
 //  - las_step_fwd: one launch per LSTM layer and step.
 //      gates = bf16(A1 @ Wt[:, :K1]^T + A2 @ Wt[:, K1:K1+K2]^T + pre)
-//    (fp32 accumulation, ONE rounding), then the cell of lstm_gates.hip on
+//    (fp32 accumulation, ONE rounding), then the cell of lstm_cell.h on
 //    the rounded gates; gates, c and m go straight into caller rows.
 //  - las_cell_bwd: the cell backward with its data-gradient GEMM as
 //    prologue,
@@ -32,14 +33,12 @@
 #include <cstdint>
 
 #include "common.h"
+#include "host_checks.h"
+#include "lstm_cell.h"
 #include "mfma.h"
 #include "tile_gemm.h"
 
 namespace {
-
-__device__ __forceinline__ float sigf(float x) {
-  return 1.f / (1.f + __expf(-x));
-}
 
 // pre is [B,4H] (pre_ld = 4H) or a [4H] vector (pre_ld = 0). a1 / a2 are
 // [B,K1] / [B,K2] with row strides lda1 / lda2; an empty range is skipped.
@@ -55,22 +54,18 @@ __global__ __launch_bounds__(256) void las_step_fwd_kernel(
     unsigned short* __restrict__ m_out, int b, int h, float fgb, float cap) {
   const int j0 = blockIdx.x * 16;
   const int m0 = blockIdx.y * (16 * MT);
-  const int wid = threadIdx.x / WAVE_SIZE;
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4;
-  const int cl = lane & 15;
+  const StepThread th = step_thread();
 
   __shared__ float rec[4][16 * MT][16];  // GEMM term per gate
 
-  // Pointwise operands of this thread's MT elements (element e is tile
-  // row e*16 + tid/16, column tid%16), loaded ahead of the GEMM as raw
-  // bits. The c_prev branch is on a kernel argument: it waits on nothing.
-  const int lc = threadIdx.x & 15;
-  const int j = j0 + lc;
+  // Pointwise operands of this thread's MT elements, loaded ahead of the
+  // GEMM as raw bits. The c_prev branch is on a kernel argument: it waits
+  // on nothing.
+  const int j = j0 + th.lc;
   unsigned short pin[MT][4], c_prev_u[MT];
 #pragma unroll
   for (int e = 0; e < MT; ++e) {
-    const int rowc = min(m0 + e * 16 + (threadIdx.x >> 4), b - 1);
+    const int rowc = min(m0 + e * 16 + th.lr, b - 1);
     const unsigned short* pr = pre + rowc * pre_ld + j;
 #pragma unroll
     for (int q = 0; q < 4; ++q) pin[e][q] = pr[q * h];
@@ -82,29 +77,23 @@ __global__ __launch_bounds__(256) void las_step_fwd_kernel(
   for (int mt = 0; mt < MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
   {
     const unsigned short* brow =
-        wt + ((long)wid * h + j0 + cl) * ldw + g * 8;
+        wt + ((long)th.wid * h + j0 + th.cl) * ldw + th.g * 8;
     const unsigned short* a1row[MT];
     const unsigned short* a2row[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      const long row = min(m0 + mt * 16 + cl, b - 1);
-      a1row[mt] = a1 + row * lda1 + g * 8;
-      a2row[mt] = a2 + row * lda2 + g * 8;
+      const long row = min(m0 + mt * 16 + th.cl, b - 1);
+      a1row[mt] = a1 + row * lda1 + th.g * 8;
+      a2row[mt] = a2 + row * lda2 + th.g * 8;
     }
     tile_gemm2<MT>(a1row, k1, a2row, k2, brow, acc);
   }
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      rec[wid][mt * 16 + g * 4 + r][cl] = acc[mt][r];
-    }
-  }
+  park_acc<MT>(rec[th.wid], th.g, th.cl, acc);
   __syncthreads();
 
 #pragma unroll
   for (int e = 0; e < MT; ++e) {
-    const int lrow = e * 16 + (threadIdx.x >> 4);
+    const int lrow = e * 16 + th.lr;
     const int row = m0 + lrow;
     if (row >= b) continue;
     unsigned short* gr = gates + (long)row * 4 * h + j;
@@ -113,18 +102,15 @@ __global__ __launch_bounds__(256) void las_step_fwd_kernel(
     for (int q = 0; q < 4; ++q) {
       // Round to bf16 first: backward recomputes from the stored value.
       const unsigned short u = float_to_bf16_bits(
-          rec[q][lrow][lc] + bf16_bits_to_float(pin[e][q]));
+          rec[q][lrow][th.lc] + bf16_bits_to_float(pin[e][q]));
       gr[q * h] = u;
       p[q] = bf16_bits_to_float(u);
     }
-    const float cand = tanhf(p[0]);
-    const float ig = sigf(p[1]);
-    const float fg = sigf(p[2] + fgb);
-    const float og = sigf(p[3]);
-    float cn = fg * bf16_bits_to_float(c_prev_u[e]) + ig * cand;
-    if (cap > 0.f) cn = fminf(cap, fmaxf(-cap, cn));
+    const LstmActs a = lstm_acts(p[0], p[1], p[2], p[3], fgb);
+    const float cn =
+        lstm_cell_update(a, bf16_bits_to_float(c_prev_u[e]), cap).c;
     c_out[(long)row * h + j] = float_to_bf16_bits(cn);
-    m_out[(long)row * h + j] = float_to_bf16_bits(og * tanhf(cn));
+    m_out[(long)row * h + j] = float_to_bf16_bits(a.og * tanhf(cn));
   }
 }
 
@@ -145,22 +131,18 @@ __global__ __launch_bounds__(256) void las_cell_bwd_kernel(
   const bool cell = n0 < h;             // else: pass-through half
   const int j0 = cell ? n0 : n0 - h;    // hidden column
   const int m0 = blockIdx.y * (16 * MT);
-  const int wid = threadIdx.x / WAVE_SIZE;
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4;
-  const int cl = lane & 15;
+  const StepThread th = step_thread();
 
   __shared__ float red[4][16 * MT][16];  // per-wave K-split partials
 
-  const int lc = threadIdx.x & 15;
-  const int j = j0 + lc;
+  const int j = j0 + th.lc;
   // Raw loads ahead of the GEMM. Every branch here is on kernel arguments
   // or blockIdx alone.
   unsigned short gin[MT][4], c_prev_u[MT], add_b_u[MT];
   float add_f_v[MT], dc_in[MT];
 #pragma unroll
   for (int e = 0; e < MT; ++e) {
-    const long rowc = min(m0 + e * 16 + (threadIdx.x >> 4), b - 1);
+    const long rowc = min(m0 + e * 16 + th.lr, b - 1);
 #pragma unroll
     for (int q = 0; q < 4; ++q) gin[e][q] = 0;
     c_prev_u[e] = 0;
@@ -180,62 +162,50 @@ __global__ __launch_bounds__(256) void las_cell_bwd_kernel(
 
   {
     const int kq = (k / 32 + 3) / 4 * 32;  // per-wave K quota (mult of 32)
-    const int k_lo = wid * kq;
+    const int k_lo = th.wid * kq;
     const int k_hi = min(k, k_lo + kq);
     f32x4 acc[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
-    const unsigned short* brow = wt + (long)(n0 + cl) * ldw + k_lo + g * 8;
+    const unsigned short* brow =
+        wt + (long)(n0 + th.cl) * ldw + k_lo + th.g * 8;
     const unsigned short* arow[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      arow[mt] = a + (long)min(m0 + mt * 16 + cl, b - 1) * lda + k_lo + g * 8;
+      arow[mt] = a + (long)min(m0 + mt * 16 + th.cl, b - 1) * lda + k_lo +
+                 th.g * 8;
     }
     tile_gemm<MT>(arow, brow, k_hi - k_lo, acc);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[wid][mt * 16 + g * 4 + r][cl] = acc[mt][r];
-      }
-    }
+    park_acc<MT>(red[th.wid], th.g, th.cl, acc);
   }
   __syncthreads();
 
 #pragma unroll
   for (int e = 0; e < MT; ++e) {
-    const int lrow = e * 16 + (threadIdx.x >> 4);
+    const int lrow = e * 16 + th.lr;
     const int row = m0 + lrow;
     if (row >= b) continue;
     const long so = (long)row * h + j;
-    const float gemm = red[0][lrow][lc] + red[1][lrow][lc] +
-                       red[2][lrow][lc] + red[3][lrow][lc];
+    const float gemm = sum_partials(red, lrow, th.lc);
     if (!cell) {
       pass_out[so] = gemm;
       continue;
     }
     const float dm = gemm + bf16_bits_to_float(add_b_u[e]) + add_f_v[e];
 
-    const float cand = tanhf(bf16_bits_to_float(gin[e][0]));
-    const float ig = sigf(bf16_bits_to_float(gin[e][1]));
-    const float fg = sigf(bf16_bits_to_float(gin[e][2]) + fgb);
-    const float og = sigf(bf16_bits_to_float(gin[e][3]));
+    // The cell recomputed in fp32 from the stored gates and c_prev.
+    const LstmActs ac = lstm_acts(
+        bf16_bits_to_float(gin[e][0]), bf16_bits_to_float(gin[e][1]),
+        bf16_bits_to_float(gin[e][2]), bf16_bits_to_float(gin[e][3]), fgb);
     const float c0v = bf16_bits_to_float(c_prev_u[e]);
-    const float craw = fg * c0v + ig * cand;
-    float cn = craw;
-    if (cap > 0.f) cn = fminf(cap, fmaxf(-cap, cn));
-    const float tc = tanhf(cn);
-
-    const float do_ = dm * tc;
-    float dc = dc_in[e] + dm * og * (1.f - tc * tc);
-    if (cap > 0.f && (craw > cap || craw < -cap)) dc = 0.f;
+    const LstmC cn = lstm_cell_update(ac, c0v, cap);
+    const LstmGrads dg =
+        lstm_cell_bwd(ac, c0v, tanhf(cn.c), cn.raw, cap, dm, dc_in[e]);
 
     unsigned short* dgr = dgates + (long)row * 4 * h + j;
-    dgr[0] = float_to_bf16_bits(dc * ig * (1.f - cand * cand));
-    dgr[h] = float_to_bf16_bits(dc * cand * ig * (1.f - ig));
-    dgr[2 * h] = float_to_bf16_bits(dc * c0v * fg * (1.f - fg));
-    dgr[3 * h] = float_to_bf16_bits(do_ * og * (1.f - og));
-    dc_carry[so] = dc * fg;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dgr[q * h] = float_to_bf16_bits(dg.dg[q]);
+    dc_carry[so] = dg.dc_prev;
   }
 }
 
@@ -243,16 +213,6 @@ __global__ __launch_bounds__(256) void las_cell_bwd_kernel(
 // Host wrappers: every dtype, shape, stride and alignment is checked
 // before the launch; nothing is allocated.
 // ---------------------------------------------------------------------------
-
-// Dense [rows, cols] tensor (a row of a contiguous stack is).
-void check_dense(const torch::Tensor& t, torch::ScalarType st, int64_t rows,
-                 int64_t cols, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == st && t.dim() == 2 &&
-                  t.size(0) == rows && t.size(1) == cols &&
-                  t.is_contiguous() && (uintptr_t)t.data_ptr() % 16 == 0,
-              name, " must be a dense CUDA [", rows, ",", cols, "] tensor of ",
-              st);
-}
 
 // bf16 [rows, K] read as MFMA fragments: unit column stride, 16-byte
 // aligned rows, K % 32 == 0. Returns the row stride.
@@ -263,31 +223,16 @@ long check_frag_rows(const torch::Tensor& t, int64_t rows, const char* name) {
   const int64_t k = t.size(1);
   TORCH_CHECK(k >= 32 && k % 32 == 0, name, ": K % 32 == 0");
   const int64_t ld = rows == 1 ? k : t.stride(0);
-  TORCH_CHECK(t.stride(1) == 1 && ld >= k && ld % 8 == 0 &&
-                  (uintptr_t)t.data_ptr() % 16 == 0,
+  TORCH_CHECK(t.stride(1) == 1 && ld >= k && ld % 8 == 0 && aligned16(t),
               name, " must have unit column stride and 16-byte aligned rows");
   return (long)ld;
 }
 
-// bf16 [rows, cols] read element-wise with a row stride.
-long check_strided_rows(const torch::Tensor& t, int64_t rows, int64_t cols,
-                        const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
-                  t.dim() == 2 && t.size(0) == rows && t.size(1) == cols &&
-                  t.stride(1) == 1 && (rows == 1 || t.stride(0) >= cols),
-              name, " must be CUDA bf16 [", rows, ",", cols,
-              "] with unit column stride");
-  return rows == 1 ? (long)cols : (long)t.stride(0);
-}
-
-// Rows per workgroup: 16 * MT. rows == 0 picks the default: 32 rows were
-// the fastest of the three for every stage at B=512, H=640
-// (docs/KERNEL_NOTES.md).
-int pick_step_mt(int64_t rows) {
-  if (rows == 0) rows = 32;
-  TORCH_CHECK(rows == 32 || rows == 64 || rows == 128,
-              "rows_per_block must be 0, 32, 64 or 128");
-  return (int)rows / 16;
+// The [rows, >= k] weight operand of both stages.
+bool weight_ok(const torch::Tensor& wt, int64_t rows, int64_t k) {
+  return cuda_contig(wt, torch::kBFloat16) && wt.dim() == 2 &&
+         wt.size(0) == rows && wt.size(1) >= k && wt.size(1) % 8 == 0 &&
+         aligned16(wt);
 }
 
 }  // namespace
@@ -319,13 +264,9 @@ void las_step_fwd(c10::optional<torch::Tensor> a1,
     k2 = a2->size(1);
     a2p = (const unsigned short*)a2->data_ptr();
   }
-  TORCH_CHECK(wt.is_cuda() && wt.scalar_type() == torch::kBFloat16 &&
-                  wt.dim() == 2 && wt.is_contiguous() &&
-                  wt.size(0) == 4 * h && wt.size(1) >= k1 + k2 &&
-                  wt.size(1) % 8 == 0 && (uintptr_t)wt.data_ptr() % 16 == 0,
+  TORCH_CHECK(weight_ok(wt, 4 * h, k1 + k2),
               "wt must be CUDA contiguous bf16 [4H, >= K1+K2], ldw % 8 == 0");
-  TORCH_CHECK(pre.is_cuda() && pre.scalar_type() == torch::kBFloat16 &&
-                  pre.is_contiguous() &&
+  TORCH_CHECK(cuda_contig(pre, torch::kBFloat16) &&
                   ((pre.dim() == 1 && pre.size(0) == 4 * h) ||
                    (pre.dim() == 2 && pre.size(0) == b &&
                     pre.size(1) == 4 * h)),
@@ -335,24 +276,17 @@ void las_step_fwd(c10::optional<torch::Tensor> a1,
     check_dense(*c_prev, torch::kBFloat16, b, h, "c_prev");
     cp = (const unsigned short*)c_prev->data_ptr();
   }
-  const int mt = pick_step_mt(rows_per_block);
+  const int mt = step_mt(rows_per_block, 2);
   const dim3 grid(h / 16, cdiv(b, 16 * mt));
   auto stream = at::cuda::getCurrentCUDAStream();
-#define LAUNCH_FWD(MT)                                                      \
-  hipLaunchKernelGGL(                                                       \
-      las_step_fwd_kernel<MT>, grid, dim3(256), 0, stream, a1p, lda1,       \
-      (int)k1, a2p, lda2, (int)k2, (const unsigned short*)wt.data_ptr(),    \
-      (long)wt.size(1), (const unsigned short*)pre.data_ptr(),              \
-      (long)(pre.dim() == 2 ? 4 * h : 0), cp,                               \
-      (unsigned short*)gates.data_ptr(), (unsigned short*)c_out.data_ptr(), \
-      (unsigned short*)m_out.data_ptr(), (int)b, (int)h, (float)fgb,        \
-      (float)cap)
-  switch (mt) {
-    case 2: LAUNCH_FWD(2); break;
-    case 4: LAUNCH_FWD(4); break;
-    default: LAUNCH_FWD(8); break;
-  }
-#undef LAUNCH_FWD
+  dispatch_mt<2>(mt, [&](auto mt_c) {
+    hipLaunchKernelGGL(
+        las_step_fwd_kernel<decltype(mt_c)::value>, grid, dim3(256), 0,
+        stream, a1p, lda1, (int)k1, a2p, lda2, (int)k2, u16(wt),
+        (long)wt.size(1), u16(pre), (long)(pre.dim() == 2 ? 4 * h : 0), cp,
+        u16(gates), u16(c_out), u16(m_out), (int)b, (int)h, (float)fgb,
+        (float)cap);
+  });
   LV_CHECK_HIP(hipGetLastError());
 }
 
@@ -374,10 +308,7 @@ void las_cell_bwd(torch::Tensor a, torch::Tensor wt,
   const long lda = check_frag_rows(a, b, "a");
   const int64_t k = a.size(1);
   const int64_t n = pass_out.has_value() ? 2 * h : h;
-  TORCH_CHECK(wt.is_cuda() && wt.scalar_type() == torch::kBFloat16 &&
-                  wt.dim() == 2 && wt.is_contiguous() && wt.size(0) == n &&
-                  wt.size(1) >= k && wt.size(1) % 8 == 0 &&
-                  (uintptr_t)wt.data_ptr() % 16 == 0,
+  TORCH_CHECK(weight_ok(wt, n, k),
               "wt must be CUDA contiguous bf16 [H or 2H, >= K], ldw % 8 == 0");
   const unsigned short* abp = nullptr;
   long ldb = 0;
@@ -400,23 +331,15 @@ void las_cell_bwd(torch::Tensor a, torch::Tensor wt,
     check_dense(*pass_out, torch::kFloat32, b, h, "pass_out");
     pp = pass_out->data_ptr<float>();
   }
-  const int mt = pick_step_mt(rows_per_block);
+  const int mt = step_mt(rows_per_block, 2);
   const dim3 grid(n / 16, cdiv(b, 16 * mt));
   auto stream = at::cuda::getCurrentCUDAStream();
-#define LAUNCH_BWD(MT)                                                     \
-  hipLaunchKernelGGL(                                                      \
-      las_cell_bwd_kernel<MT>, grid, dim3(256), 0, stream,                 \
-      (const unsigned short*)a.data_ptr(), lda, (int)k,                    \
-      (const unsigned short*)wt.data_ptr(), (long)wt.size(1), abp, ldb,    \
-      afp, (const unsigned short*)gates.data_ptr(), cp,                    \
-      dc_carry.data_ptr<float>(), (int)has_dc,                             \
-      (unsigned short*)dgates.data_ptr(), pp, (int)b, (int)h, (float)fgb,  \
-      (float)cap)
-  switch (mt) {
-    case 2: LAUNCH_BWD(2); break;
-    case 4: LAUNCH_BWD(4); break;
-    default: LAUNCH_BWD(8); break;
-  }
-#undef LAUNCH_BWD
+  dispatch_mt<2>(mt, [&](auto mt_c) {
+    hipLaunchKernelGGL(
+        las_cell_bwd_kernel<decltype(mt_c)::value>, grid, dim3(256), 0,
+        stream, u16(a), lda, (int)k, u16(wt), (long)wt.size(1), abp, ldb, afp,
+        u16(gates), cp, dc_carry.data_ptr<float>(), (int)has_dc, u16(dgates),
+        pp, (int)b, (int)h, (float)fgb, (float)cap);
+  });
   LV_CHECK_HIP(hipGetLastError());
 }

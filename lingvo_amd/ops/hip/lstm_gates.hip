@@ -1,23 +1,24 @@
-// Fused LSTM gate pointwise math for gfx950 (reference cell
-// math: lingvo/core/rnn_cell.py:213 LSTMCellSimple).
-//
-//   i=sig(g1), f=sig(g2+fgb), o=sig(g3), cand=tanh(g0)
-//   c1 = clamp(f*c0 + i*cand, +-cap);  m1 = o * tanh(c1)
-//
-// One kernel fwd / one bwd (recomputing activations from saved gates)
-// replaces the ~12 eager pointwise kernels per step of the teacher-
-// forced decoder loop. Gate order matches LSTMCellSimple: [i_i(cand),
-// i_g(i), f_g(f), o_g(o)].
+// Fused LSTM gate pointwise math for gfx950: the cell of
+// lstm_cell.h on stored gates, one kernel fwd / one bwd (recomputing
+// activations from saved gates), replacing the ~12 eager pointwise kernels
+// per step of the 'split' decoder loop and of the per-step cell layers.
 
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 
 #include "common.h"
+#include "host_checks.h"
+#include "lstm_cell.h"
 
 namespace {
 
-__device__ __forceinline__ float sigf(float x) {
-  return 1.f / (1.f + __expf(-x));
+// gr: the [4H] gate row of this element, col its hidden column.
+__device__ __forceinline__ LstmActs load_acts(const unsigned short* gr,
+                                              long col, int h, float fgb) {
+  return lstm_acts(
+      bf16_bits_to_float(gr[col]), bf16_bits_to_float(gr[h + col]),
+      bf16_bits_to_float(gr[2 * h + col]),
+      bf16_bits_to_float(gr[3 * h + col]), fgb);
 }
 
 __global__ void lstm_gates_fwd(const unsigned short* __restrict__ gates,
@@ -29,15 +30,10 @@ __global__ void lstm_gates_fwd(const unsigned short* __restrict__ gates,
        i += (long)gridDim.x * blockDim.x) {
     const long row = i / h;
     const long col = i % h;
-    const unsigned short* gr = gates + row * 4 * h;
-    float cand = tanhf(bf16_bits_to_float(gr[col]));
-    float ig = sigf(bf16_bits_to_float(gr[h + col]));
-    float fg = sigf(bf16_bits_to_float(gr[2 * h + col]) + fgb);
-    float og = sigf(bf16_bits_to_float(gr[3 * h + col]));
-    float c = fg * bf16_bits_to_float(c0[i]) + ig * cand;
-    if (cap > 0.f) c = fminf(cap, fmaxf(-cap, c));
+    const LstmActs a = load_acts(gates + row * 4 * h, col, h, fgb);
+    const float c = lstm_cell_update(a, bf16_bits_to_float(c0[i]), cap).c;
     c1[i] = float_to_bf16_bits(c);
-    m1[i] = float_to_bf16_bits(og * tanhf(c));
+    m1[i] = float_to_bf16_bits(a.og * tanhf(c));
   }
 }
 
@@ -53,32 +49,40 @@ __global__ void lstm_gates_bwd(const unsigned short* __restrict__ gates,
        i += (long)gridDim.x * blockDim.x) {
     const long row = i / h;
     const long col = i % h;
-    const unsigned short* gr = gates + row * 4 * h;
-    float cand = tanhf(bf16_bits_to_float(gr[col]));
-    float ig = sigf(bf16_bits_to_float(gr[h + col]));
-    float fg = sigf(bf16_bits_to_float(gr[2 * h + col]) + fgb);
-    float og = sigf(bf16_bits_to_float(gr[3 * h + col]));
-    float c0v = bf16_bits_to_float(c0[i]);
-    float cv = bf16_bits_to_float(c1[i]);  // post-clamp value
-    float tc = tanhf(cv);
-    float dm = bf16_bits_to_float(dm1[i]);
-    float dc = dc1_ext ? bf16_bits_to_float(dc1_ext[i]) : 0.f;
-    float do_ = dm * tc;
-    dc += dm * og * (1.f - tc * tc);
-    if (cap > 0.f) {
-      float pre = fg * c0v + ig * cand;  // pre-clamp
-      if (pre > cap || pre < -cap) dc = 0.f;
-    }
-    float di = dc * cand;
-    float dcand = dc * ig;
-    float df = dc * c0v;
+    const LstmActs a = load_acts(gates + row * 4 * h, col, h, fgb);
+    const float c0v = bf16_bits_to_float(c0[i]);
+    // tanh of the STORED (bf16, post-clamp) c1, unlike the step kernels,
+    // which recompute c in fp32; the clamp test is on the recomputed c.
+    const float tc = tanhf(bf16_bits_to_float(c1[i]));
+    const float dm = bf16_bits_to_float(dm1[i]);
+    const float dc = dc1_ext ? bf16_bits_to_float(dc1_ext[i]) : 0.f;
+    const LstmGrads d = lstm_cell_bwd(
+        a, c0v, tc, lstm_cell_update(a, c0v, cap).raw, cap, dm, dc);
     unsigned short* dgr = dgates + row * 4 * h;
-    dgr[col] = float_to_bf16_bits(dcand * (1.f - cand * cand));
-    dgr[h + col] = float_to_bf16_bits(di * ig * (1.f - ig));
-    dgr[2 * h + col] = float_to_bf16_bits(df * fg * (1.f - fg));
-    dgr[3 * h + col] = float_to_bf16_bits(do_ * og * (1.f - og));
-    dc0[i] = float_to_bf16_bits(dc * fg);
+    dgr[col] = float_to_bf16_bits(d.dg[0]);
+    dgr[h + col] = float_to_bf16_bits(d.dg[1]);
+    dgr[2 * h + col] = float_to_bf16_bits(d.dg[2]);
+    dgr[3 * h + col] = float_to_bf16_bits(d.dg[3]);
+    dc0[i] = float_to_bf16_bits(d.dc_prev);
   }
+}
+
+// gates [..., 4H] and c0 [..., H], both contiguous bf16 on the device.
+void check_gates_c0(const torch::Tensor& gates, const torch::Tensor& c0) {
+  check_contig(gates, torch::kBFloat16, "gates");
+  check_contig(c0, torch::kBFloat16, "c0");
+  const int64_t nd = c0.dim();
+  TORCH_CHECK(nd >= 1 && gates.dim() == nd &&
+                  gates.sizes().slice(0, nd - 1) ==
+                      c0.sizes().slice(0, nd - 1) &&
+                  gates.size(-1) == 4 * c0.size(-1),
+              "gates must be [..., 4H] for c0 [..., H]");
+}
+
+void check_like_c0(const torch::Tensor& t, const torch::Tensor& c0,
+                   const char* name) {
+  check_contig(t, torch::kBFloat16, name);
+  TORCH_CHECK(t.sizes() == c0.sizes(), name, " must have the shape of c0");
 }
 
 }  // namespace
@@ -86,20 +90,15 @@ __global__ void lstm_gates_bwd(const unsigned short* __restrict__ gates,
 std::vector<torch::Tensor> lstm_gates_fwd_op(torch::Tensor gates,
                                              torch::Tensor c0, double fgb,
                                              double cap) {
-  TORCH_CHECK(gates.is_cuda() && gates.is_contiguous() &&
-              gates.scalar_type() == torch::kBFloat16);
+  check_gates_c0(gates, c0);
   const long n = c0.numel();
   const int h = c0.size(-1);
   auto c1 = torch::empty_like(c0);
   auto m1 = torch::empty_like(c0);
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(lstm_gates_fwd, dim3(memory_bound_grid(n, 256)),
-                     dim3(256), 0, stream,
-                     (const unsigned short*)gates.data_ptr(),
-                     (const unsigned short*)c0.data_ptr(),
-                     (unsigned short*)c1.data_ptr(),
-                     (unsigned short*)m1.data_ptr(), n, h, (float)fgb,
-                     (float)cap);
+                     dim3(256), 0, stream, u16(gates), u16(c0), u16(c1),
+                     u16(m1), n, h, (float)fgb, (float)cap);
   return {c1, m1};
 }
 
@@ -107,22 +106,18 @@ std::vector<torch::Tensor> lstm_gates_bwd_op(
     torch::Tensor gates, torch::Tensor c0, torch::Tensor c1,
     torch::Tensor dm1, c10::optional<torch::Tensor> dc1, double fgb,
     double cap) {
+  check_gates_c0(gates, c0);
+  check_like_c0(c1, c0, "c1");
+  check_like_c0(dm1, c0, "dm1");
+  if (dc1.has_value()) check_like_c0(*dc1, c0, "dc1");
   const long n = c0.numel();
   const int h = c0.size(-1);
   auto dgates = torch::empty_like(gates);
   auto dc0 = torch::empty_like(c0);
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(lstm_gates_bwd, dim3(memory_bound_grid(n, 256)),
-                     dim3(256), 0, stream,
-                     (const unsigned short*)gates.data_ptr(),
-                     (const unsigned short*)c0.data_ptr(),
-                     (const unsigned short*)c1.data_ptr(),
-                     (const unsigned short*)dm1.data_ptr(),
-                     dc1.has_value()
-                         ? (const unsigned short*)dc1->data_ptr()
-                         : nullptr,
-                     (unsigned short*)dgates.data_ptr(),
-                     (unsigned short*)dc0.data_ptr(), n, h, (float)fgb,
-                     (float)cap);
+                     dim3(256), 0, stream, u16(gates), u16(c0), u16(c1),
+                     u16(dm1), dc1.has_value() ? u16(*dc1) : nullptr,
+                     u16(dgates), u16(dc0), n, h, (float)fgb, (float)cap);
   return {dgates, dc0};
 }

@@ -36,14 +36,12 @@
 #include <torch/extension.h>
 
 #include "common.h"
+#include "host_checks.h"
+#include "lstm_cell.h"
 #include "mfma.h"
 #include "tile_gemm.h"
 
 namespace {
-
-__device__ __forceinline__ float sigf(float x) {
-  return 1.f / (1.f + __expf(-x));
-}
 
 // ---------------------------------------------------------------------------
 // Forward step. Wave w computes gate w's 16 columns for all MT m-tiles
@@ -63,20 +61,15 @@ __global__ __launch_bounds__(256) void lstm_scan_step_fwd(
   const int t = rev ? t_len - 1 - s : s;
   const int t_prev = rev ? t + 1 : t - 1;
   const bool has_prev = s > 0;
-  const int wid = threadIdx.x / WAVE_SIZE;
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4;
-  const int cl = lane & 15;
+  const StepThread th = step_thread();
 
   __shared__ float rec[4][16 * MT][16];  // recurrent term per gate
 
   const long st = ((long)d * t_len + t) * b;         // row base at t
   const long sp = ((long)d * t_len + t_prev) * b;    // row base at t_prev
 
-  // Pointwise operands of this thread's MT elements (element e is tile
-  // row e*16 + tid/16, column tid%16), loaded ahead of the GEMM.
-  const int lc = threadIdx.x & 15;
-  const int j = j0 + lc;
+  // Pointwise operands of this thread's MT elements, ahead of the GEMM.
+  const int j = j0 + th.lc;
   // Every load is unconditional and kept as raw bits: a branch or a
   // conversion here would wait for these loads before the GEMM has issued
   // its own. Without a previous step the state loads read (and discard)
@@ -86,7 +79,7 @@ __global__ __launch_bounds__(256) void lstm_scan_step_fwd(
   float pv[MT];
 #pragma unroll
   for (int e = 0; e < MT; ++e) {
-    const int rowc = min(m0 + e * 16 + (threadIdx.x >> 4), b - 1);
+    const int rowc = min(m0 + e * 16 + th.lr, b - 1);
     const unsigned short* gr = gates + (st + rowc) * 4 * h + j;
 #pragma unroll
     for (int q = 0; q < 4; ++q) gin[e][q] = gr[q * h];
@@ -100,26 +93,20 @@ __global__ __launch_bounds__(256) void lstm_scan_step_fwd(
   for (int mt = 0; mt < MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
   if (has_prev) {
     const unsigned short* brow =
-        wmt + ((long)d * 4 * h + (long)wid * h + j0 + cl) * h + g * 8;
+        wmt + ((long)d * 4 * h + (long)th.wid * h + j0 + th.cl) * h + th.g * 8;
     const unsigned short* arow[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      arow[mt] = m + (sp + min(m0 + mt * 16 + cl, b - 1)) * h + g * 8;
+      arow[mt] = m + (sp + min(m0 + mt * 16 + th.cl, b - 1)) * h + th.g * 8;
     }
     tile_gemm<MT>(arow, brow, h, acc);
   }
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      rec[wid][mt * 16 + g * 4 + r][cl] = acc[mt][r];
-    }
-  }
+  park_acc<MT>(rec[th.wid], th.g, th.cl, acc);
   __syncthreads();
 
 #pragma unroll
   for (int e = 0; e < MT; ++e) {
-    const int lrow = e * 16 + (threadIdx.x >> 4);
+    const int lrow = e * 16 + th.lr;
     const int row = m0 + lrow;
     if (row >= b) continue;
     unsigned short* gr = gates + (st + row) * 4 * h + j;
@@ -129,19 +116,16 @@ __global__ __launch_bounds__(256) void lstm_scan_step_fwd(
       // Round to bf16 first: backward recomputes from the stored value.
       const unsigned short u =
           float_to_bf16_bits(bf16_bits_to_float(gin[e][q]) +
-                             rec[q][lrow][lc]);
+                             rec[q][lrow][th.lc]);
       gr[q * h] = u;
       pre[q] = bf16_bits_to_float(u);
     }
-    const float cand = tanhf(pre[0]);
-    const float ig = sigf(pre[1]);
-    const float fg = sigf(pre[2] + fgb);
-    const float og = sigf(pre[3]);
+    const LstmActs a = lstm_acts(pre[0], pre[1], pre[2], pre[3], fgb);
     const float c_prev = has_prev ? bf16_bits_to_float(c_prev_u[e]) : 0.f;
     const float m_prev = has_prev ? bf16_bits_to_float(m_prev_u[e]) : 0.f;
-    float cn = fg * c_prev + ig * cand;
-    if (cap > 0.f) cn = fminf(cap, fmaxf(-cap, cn));
-    const float mn = og * tanhf(cn);
+    const float cn = lstm_cell_update(a, c_prev, cap).c;
+    const float mn = a.og * tanhf(cn);
+    // Padding blend: a padded step (p = 1) carries the state through.
     const float p = pv[e];
     c[(st + row) * h + j] =
         float_to_bf16_bits(cn * (1.f - p) + c_prev * p);
@@ -176,10 +160,7 @@ __global__ __launch_bounds__(256) void lstm_scan_step_bwd(
   const int t_next = rev ? t - 1 : t + 1;
   const bool has_prev = s > 0;
   const bool has_next = s < t_len - 1;
-  const int wid = threadIdx.x / WAVE_SIZE;
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4;
-  const int cl = lane & 15;
+  const StepThread th = step_thread();
 
   __shared__ float red[4][16 * MT][16];  // per-wave K-split partials
 
@@ -188,8 +169,7 @@ __global__ __launch_bounds__(256) void lstm_scan_step_bwd(
   const long sn = ((long)d * t_len + t_next) * b;
 
   // Pointwise operands of this thread's MT elements, ahead of the GEMM.
-  const int lc = threadIdx.x & 15;
-  const int j = j0 + lc;
+  const int j = j0 + th.lc;
   // Unconditional raw loads, as in the forward kernel: what a missing
   // input would have supplied is read from a valid stand-in (c for a null
   // dm_out / dc_out, this step's slot for a missing previous step, the
@@ -202,7 +182,7 @@ __global__ __launch_bounds__(256) void lstm_scan_step_bwd(
   float pv[MT], dm_in[MT], dc_in[MT];
 #pragma unroll
   for (int e = 0; e < MT; ++e) {
-    const int rowc = min(m0 + e * 16 + (threadIdx.x >> 4), b - 1);
+    const int rowc = min(m0 + e * 16 + th.lr, b - 1);
     const unsigned short* gr = gates + (st + rowc) * 4 * h + j;
     const long co = ((long)d * b + rowc) * h + j;  // [D,B,H] carry offset
 #pragma unroll
@@ -219,28 +199,22 @@ __global__ __launch_bounds__(256) void lstm_scan_step_bwd(
     f32x4 acc[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
-    const unsigned short* brow =
-        wm + ((long)d * h + j0 + cl) * 4 * h + (long)wid * h + g * 8;
+    const unsigned short* brow = wm + ((long)d * h + j0 + th.cl) * 4 * h +
+                                 (long)th.wid * h + th.g * 8;
     const unsigned short* arow[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      arow[mt] = dgates + (sn + min(m0 + mt * 16 + cl, b - 1)) * 4 * h +
-                 (long)wid * h + g * 8;
+      arow[mt] = dgates + (sn + min(m0 + mt * 16 + th.cl, b - 1)) * 4 * h +
+                 (long)th.wid * h + th.g * 8;
     }
     tile_gemm<MT>(arow, brow, h, acc);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[wid][mt * 16 + g * 4 + r][cl] = acc[mt][r];
-      }
-    }
+    park_acc<MT>(red[th.wid], th.g, th.cl, acc);
   }
   __syncthreads();
 
 #pragma unroll
   for (int e = 0; e < MT; ++e) {
-    const int lrow = e * 16 + (threadIdx.x >> 4);
+    const int lrow = e * 16 + th.lr;
     const int row = m0 + lrow;
     if (row >= b) continue;
     const long co = ((long)d * b + row) * h + j;
@@ -248,55 +222,55 @@ __global__ __launch_bounds__(256) void lstm_scan_step_bwd(
     float dmt = dm_out ? bf16_bits_to_float(dm_out_u[e]) : 0.f;
     float dct = dc_out ? bf16_bits_to_float(dc_out_u[e]) : 0.f;
     if (has_next) {
-      dmt += red[0][lrow][lc] + red[1][lrow][lc] + red[2][lrow][lc] +
-             red[3][lrow][lc] + dm_in[e];
+      dmt += sum_partials(red, lrow, th.lc) + dm_in[e];
       dct += dc_in[e];
     }
 
-    const float cand = tanhf(bf16_bits_to_float(gin[e][0]));
-    const float ig = sigf(bf16_bits_to_float(gin[e][1]));
-    const float fg = sigf(bf16_bits_to_float(gin[e][2]) + fgb);
-    const float og = sigf(bf16_bits_to_float(gin[e][3]));
+    const LstmActs a = lstm_acts(
+        bf16_bits_to_float(gin[e][0]), bf16_bits_to_float(gin[e][1]),
+        bf16_bits_to_float(gin[e][2]), bf16_bits_to_float(gin[e][3]), fgb);
     const float c_prev = has_prev ? bf16_bits_to_float(c_prev_u[e]) : 0.f;
     // c~ from this recomputation: the stored c[t] is post-blend.
-    const float craw = fg * c_prev + ig * cand;
-    float cn = craw;
-    if (cap > 0.f) cn = fminf(cap, fmaxf(-cap, cn));
-    const float tc = tanhf(cn);
-
-    const float dml = (1.f - p) * dmt;  // live (unpadded) share
-    const float do_ = dml * tc;
-    float dc = (1.f - p) * dct + dml * og * (1.f - tc * tc);
-    if (cap > 0.f && (craw > cap || craw < -cap)) dc = 0.f;
+    const LstmC cn = lstm_cell_update(a, c_prev, cap);
+    // Padding blend: the live share (1 - p) of dm and dc goes through the
+    // cell, the padded share p straight to the previous step.
+    const LstmGrads dg = lstm_cell_bwd(a, c_prev, tanhf(cn.c), cn.raw, cap,
+                                       (1.f - p) * dmt, (1.f - p) * dct);
 
     unsigned short* dgr = dgates + (st + row) * 4 * h + j;
-    dgr[0] = float_to_bf16_bits(dc * ig * (1.f - cand * cand));
-    dgr[h] = float_to_bf16_bits(dc * cand * ig * (1.f - ig));
-    dgr[2 * h] = float_to_bf16_bits(dc * c_prev * fg * (1.f - fg));
-    dgr[3 * h] = float_to_bf16_bits(do_ * og * (1.f - og));
-    dc_carry[co] = dc * fg + p * dct;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dgr[q * h] = float_to_bf16_bits(dg.dg[q]);
+    dc_carry[co] = dg.dc_prev + p * dct;
     dm_pass[co] = p * dmt;
   }
 }
 
-void check_bf16(const torch::Tensor& x, const char* name) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
-                  x.scalar_type() == torch::kBFloat16,
-              name, " must be a contiguous bf16 device tensor");
-}
+constexpr auto kBf16 = torch::kBFloat16;
+constexpr auto kF32 = torch::kFloat32;
 
-void check_f32(const torch::Tensor& x, const char* name) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
-                  x.scalar_type() == torch::kFloat32,
-              name, " must be a contiguous fp32 device tensor");
-}
+struct ScanDims {
+  int dn, t, b, h;
+};
 
-// Rows per workgroup: 16 * MT. rows == 0 picks the default.
-int pick_mt(int64_t rows) {
-  if (rows == 0) rows = 32;
-  TORCH_CHECK(rows == 16 || rows == 32 || rows == 64 || rows == 128,
-              "rows_per_block must be 0, 16, 32, 64 or 128");
-  return (int)rows / 16;
+// The operands, step range and direction mask both sweeps take.
+ScanDims check_scan(const torch::Tensor& gates, const torch::Tensor& c,
+                    const torch::Tensor& pad, int64_t rev_mask,
+                    int64_t s_begin, int64_t s_end) {
+  check_contig(gates, kBf16, "gates");
+  check_contig(c, kBf16, "c");
+  check_contig(pad, kF32, "pad");
+  TORCH_CHECK(gates.dim() == 4 && c.dim() == 4, "gates/c must be 4-D");
+  const int dn = gates.size(0), t = gates.size(1), b = gates.size(2);
+  const int h = c.size(3);
+  TORCH_CHECK(h % 32 == 0, "H % 32 == 0");
+  TORCH_CHECK(dn >= 1 && dn <= 2 && t >= 1 && b >= 1, "bad D/T/B");
+  TORCH_CHECK(gates.size(3) == 4 * h, "gates last dim must be 4H");
+  TORCH_CHECK(c.sizes() == torch::IntArrayRef({dn, t, b, h}), "c shape");
+  TORCH_CHECK(pad.sizes() == torch::IntArrayRef({t, b}), "pad shape");
+  TORCH_CHECK(0 <= s_begin && s_begin <= s_end && s_end <= t, "step range");
+  TORCH_CHECK(rev_mask >= 0 && (rev_mask >> dn) == 0,
+              "rev_mask has bits beyond the D directions");
+  return {dn, t, b, h};
 }
 
 }  // namespace
@@ -306,45 +280,25 @@ void lstm_scan_fwd(torch::Tensor gates, torch::Tensor c, torch::Tensor m,
                    torch::Tensor pad, torch::Tensor wmt, int64_t rev_mask,
                    double fgb, double cap, int64_t s_begin, int64_t s_end,
                    int64_t rows_per_block) {
-  check_bf16(gates, "gates");
-  check_bf16(c, "c");
-  check_bf16(m, "m");
-  check_bf16(wmt, "WmT");
-  check_f32(pad, "pad");
-  TORCH_CHECK(gates.dim() == 4 && c.dim() == 4, "gates/c must be 4-D");
-  const int dn = gates.size(0), t = gates.size(1), b = gates.size(2);
-  const int h = c.size(3);
-  TORCH_CHECK(h % 32 == 0, "H % 32 == 0");
-  TORCH_CHECK(dn >= 1 && dn <= 2 && t >= 1 && b >= 1, "bad D/T/B");
-  TORCH_CHECK(gates.size(3) == 4 * h, "gates last dim must be 4H");
-  TORCH_CHECK(c.sizes() == torch::IntArrayRef({dn, t, b, h}), "c shape");
+  const ScanDims z = check_scan(gates, c, pad, rev_mask, s_begin, s_end);
+  const int dn = z.dn, t = z.t, b = z.b, h = z.h;
+  check_contig(m, kBf16, "m");
+  check_contig(wmt, kBf16, "WmT");
   TORCH_CHECK(m.sizes() == c.sizes(), "m shape");
-  TORCH_CHECK(pad.sizes() == torch::IntArrayRef({t, b}), "pad shape");
   TORCH_CHECK(wmt.sizes() == torch::IntArrayRef({dn, 4 * h, h}),
               "WmT shape");
-  TORCH_CHECK(0 <= s_begin && s_begin <= s_end && s_end <= t, "step range");
-  TORCH_CHECK(rev_mask >= 0 && (rev_mask >> dn) == 0,
-              "rev_mask has bits beyond the D directions");
-  const int mt = pick_mt(rows_per_block);
+  const int mt = step_mt(rows_per_block, 1);
   const dim3 grid(h / 16, cdiv(b, 16 * mt), dn);
   auto stream = at::cuda::getCurrentCUDAStream();
-#define LAUNCH_FWD(MT)                                                     \
-  hipLaunchKernelGGL(                                                      \
-      lstm_scan_step_fwd<MT>, grid, dim3(256), 0, stream,                  \
-      (unsigned short*)gates.data_ptr(), (unsigned short*)c.data_ptr(),    \
-      (unsigned short*)m.data_ptr(), pad.data_ptr<float>(),                \
-      (const unsigned short*)wmt.data_ptr(), t, b, h, s, (int)rev_mask,    \
-      (float)fgb, (float)cap)
   for (int s = (int)s_begin; s < (int)s_end; ++s) {
-    switch (mt) {
-      case 1: LAUNCH_FWD(1); break;
-      case 2: LAUNCH_FWD(2); break;
-      case 4: LAUNCH_FWD(4); break;
-      default: LAUNCH_FWD(8); break;
-    }
+    dispatch_mt<1>(mt, [&](auto mt_c) {
+      hipLaunchKernelGGL(
+          lstm_scan_step_fwd<decltype(mt_c)::value>, grid, dim3(256), 0,
+          stream, u16(gates), u16(c), u16(m), pad.data_ptr<float>(),
+          u16(wmt), t, b, h, s, (int)rev_mask, (float)fgb, (float)cap);
+    });
     LV_CHECK_HIP(hipGetLastError());
   }
-#undef LAUNCH_FWD
 }
 
 // Runs scan steps s_end-1 .. s_begin (descending), one launch per step.
@@ -357,22 +311,13 @@ void lstm_scan_bwd(torch::Tensor gates, torch::Tensor c, torch::Tensor pad,
                    torch::Tensor dm_pass, int64_t rev_mask, double fgb,
                    double cap, int64_t s_begin, int64_t s_end,
                    int64_t rows_per_block) {
-  check_bf16(gates, "gates");
-  check_bf16(c, "c");
-  check_bf16(wm, "Wm");
-  check_bf16(dgates, "dgates");
-  check_f32(pad, "pad");
-  check_f32(dc_carry, "dc_carry");
-  check_f32(dm_pass, "dm_pass");
-  TORCH_CHECK(gates.dim() == 4 && c.dim() == 4, "gates/c must be 4-D");
-  const int dn = gates.size(0), t = gates.size(1), b = gates.size(2);
-  const int h = c.size(3);
-  TORCH_CHECK(h % 32 == 0, "H % 32 == 0");
-  TORCH_CHECK(dn >= 1 && dn <= 2 && t >= 1 && b >= 1, "bad D/T/B");
-  TORCH_CHECK(gates.size(3) == 4 * h, "gates last dim must be 4H");
-  TORCH_CHECK(c.sizes() == torch::IntArrayRef({dn, t, b, h}), "c shape");
+  const ScanDims z = check_scan(gates, c, pad, rev_mask, s_begin, s_end);
+  const int dn = z.dn, t = z.t, b = z.b, h = z.h;
+  check_contig(wm, kBf16, "Wm");
+  check_contig(dgates, kBf16, "dgates");
+  check_contig(dc_carry, kF32, "dc_carry");
+  check_contig(dm_pass, kF32, "dm_pass");
   TORCH_CHECK(dgates.sizes() == gates.sizes(), "dgates shape");
-  TORCH_CHECK(pad.sizes() == torch::IntArrayRef({t, b}), "pad shape");
   TORCH_CHECK(wm.sizes() == torch::IntArrayRef({dn, h, 4 * h}), "Wm shape");
   TORCH_CHECK(dc_carry.sizes() == torch::IntArrayRef({dn, b, h}) &&
                   dm_pass.sizes() == dc_carry.sizes(),
@@ -380,38 +325,27 @@ void lstm_scan_bwd(torch::Tensor gates, torch::Tensor c, torch::Tensor pad,
   const unsigned short* dmp = nullptr;
   const unsigned short* dcp = nullptr;
   if (dm_out.has_value()) {
-    check_bf16(*dm_out, "dm_out");
+    check_contig(*dm_out, kBf16, "dm_out");
     TORCH_CHECK(dm_out->sizes() == c.sizes(), "dm_out shape");
     dmp = (const unsigned short*)dm_out->data_ptr();
   }
   if (dc_out.has_value()) {
-    check_bf16(*dc_out, "dc_out");
+    check_contig(*dc_out, kBf16, "dc_out");
     TORCH_CHECK(dc_out->sizes() == c.sizes(), "dc_out shape");
     dcp = (const unsigned short*)dc_out->data_ptr();
   }
-  TORCH_CHECK(0 <= s_begin && s_begin <= s_end && s_end <= t, "step range");
-  TORCH_CHECK(rev_mask >= 0 && (rev_mask >> dn) == 0,
-              "rev_mask has bits beyond the D directions");
-  const int mt = pick_mt(rows_per_block);
+  const int mt = step_mt(rows_per_block, 1);
   const dim3 grid(h / 16, cdiv(b, 16 * mt), dn);
   auto stream = at::cuda::getCurrentCUDAStream();
-#define LAUNCH_BWD(MT)                                                     \
-  hipLaunchKernelGGL(                                                      \
-      lstm_scan_step_bwd<MT>, grid, dim3(256), 0, stream,                  \
-      (const unsigned short*)gates.data_ptr(),                             \
-      (const unsigned short*)c.data_ptr(), pad.data_ptr<float>(),          \
-      (const unsigned short*)wm.data_ptr(), dmp, dcp,                      \
-      (unsigned short*)dgates.data_ptr(), dc_carry.data_ptr<float>(),      \
-      dm_pass.data_ptr<float>(), t, b, h, s, (int)rev_mask, (float)fgb,    \
-      (float)cap)
   for (int s = (int)s_end - 1; s >= (int)s_begin; --s) {
-    switch (mt) {
-      case 1: LAUNCH_BWD(1); break;
-      case 2: LAUNCH_BWD(2); break;
-      case 4: LAUNCH_BWD(4); break;
-      default: LAUNCH_BWD(8); break;
-    }
+    dispatch_mt<1>(mt, [&](auto mt_c) {
+      hipLaunchKernelGGL(
+          lstm_scan_step_bwd<decltype(mt_c)::value>, grid, dim3(256), 0,
+          stream, u16(gates), u16(c), pad.data_ptr<float>(), u16(wm), dmp,
+          dcp, u16(dgates), dc_carry.data_ptr<float>(),
+          dm_pass.data_ptr<float>(), t, b, h, s, (int)rev_mask, (float)fgb,
+          (float)cap);
+    });
     LV_CHECK_HIP(hipGetLastError());
   }
-#undef LAUNCH_BWD
 }

@@ -41,11 +41,23 @@ def _step_times(s: int, t_len: int, rev: bool) -> Tuple[int, int, int]:
   return s, s - 1, s + 1
 
 
+def _cell_torch(g, c_prev, fgb, cap):
+  """Torch twin of ops/hip/lstm_cell.h: the activations (cand, i, f, o) and
+  the cell value before and after the clamp."""
+  h = g.shape[-1] // 4
+  cand = torch.tanh(g[:, :h])
+  ig = torch.sigmoid(g[:, h:2 * h])
+  fg = torch.sigmoid(g[:, 2 * h:3 * h] + fgb)
+  og = torch.sigmoid(g[:, 3 * h:])
+  craw = fg * c_prev + ig * cand
+  cn = craw.clamp(-cap, cap) if cap > 0 else craw
+  return cand, ig, fg, og, craw, cn
+
+
 def _fwd_steps_torch(gates, c, m, pad, wm_rec, fgb, cap, revs):
   """Torch twin of lstm_scan_step_fwd, all steps. gates is updated in
   place to the full pre-activations."""
-  dn, t_len, _, g4 = gates.shape
-  h = g4 // 4
+  dn, t_len = gates.shape[:2]
   for s in range(t_len):
     for d in range(dn):
       t, tp, _ = _step_times(s, t_len, revs[d])
@@ -55,14 +67,7 @@ def _fwd_steps_torch(gates, c, m, pad, wm_rec, fgb, cap, revs):
       else:
         c_prev = torch.zeros_like(c[d, t])
         m_prev = c_prev
-      g = gates[d, t]
-      cand = torch.tanh(g[:, :h])
-      ig = torch.sigmoid(g[:, h:2 * h])
-      fg = torch.sigmoid(g[:, 2 * h:3 * h] + fgb)
-      og = torch.sigmoid(g[:, 3 * h:])
-      cn = fg * c_prev + ig * cand
-      if cap > 0:
-        cn = cn.clamp(-cap, cap)
+      _, _, _, og, _, cn = _cell_torch(gates[d, t], c_prev, fgb, cap)
       mn = og * torch.tanh(cn)
       p = pad[t].unsqueeze(-1)
       c[d, t] = cn * (1 - p) + c_prev * p
@@ -86,15 +91,9 @@ def _bwd_steps_torch(gates, c, pad, wm_rec, dm_out, dc_out, dgates, fgb,
       if s < t_len - 1:
         dm_tot = dm_tot + dgates[d, tn] @ wm_rec[d].t() + dm_pass
         dc_tot = dc_tot + dc_carry
-      g = gates[d, t]
-      cand = torch.tanh(g[:, :h])
-      ig = torch.sigmoid(g[:, h:2 * h])
-      fg = torch.sigmoid(g[:, 2 * h:3 * h] + fgb)
-      og = torch.sigmoid(g[:, 3 * h:])
-      c_prev = c[d, tp] if s > 0 else torch.zeros_like(cand)
+      c_prev = c[d, tp] if s > 0 else torch.zeros_like(c[d, t])
       # c~ from this recomputation: the stored c[t] is post-blend.
-      craw = fg * c_prev + ig * cand
-      cn = craw.clamp(-cap, cap) if cap > 0 else craw
+      cand, ig, fg, og, craw, cn = _cell_torch(gates[d, t], c_prev, fgb, cap)
       tc = torch.tanh(cn)
       dmt = (1 - p) * dm_tot
       do_ = dmt * tc
