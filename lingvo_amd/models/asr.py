@@ -438,6 +438,9 @@ class CtcDecoder(BaseLayer):
     p.Define('ctc_impl', 'auto',
              "ops.ctc.ctc_loss impl: 'auto' (HIP kernels on GPU, torch twin "
              "on CPU) or 'torch' (torch.nn.functional.ctc_loss).")
+    p.Define('align_impl', 'auto',
+             "ops.ctc.ctc_forced_align impl: 'auto' (HIP kernels on GPU, "
+             "torch twin on CPU) or 'torch' (the twin on either device).")
     return p
 
   def __init__(self, params):
@@ -481,6 +484,22 @@ class CtcDecoder(BaseLayer):
         ctc_valid_fraction=(valid.mean(),
                             torch.tensor(float(valid.shape[0]))))
     return metrics, NestedMap(per_example_xent=nll)
+
+  def Align(self, theta: NestedMap, enc: torch.Tensor,
+            enc_paddings: torch.Tensor, targets: NestedMap) -> NestedMap:
+    """Forced alignment of targets.ids to the encoder frames: the best
+    single CTC path (ops.ctc.ctc_forced_align). Returns frame_ids [B,T'],
+    token_start / token_end / token_logp [B,L], score [B] and valid [B];
+    spans are in encoder frames, token_end one past the last frame. No
+    dropout, no gradient and no host sync."""
+    from lingvo_amd.ops import ctc as ctc_ops
+    p = self.p
+    al = ctc_ops.ctc_forced_align(
+        self._Logits(theta, enc).contiguous(),
+        py_utils.LengthsFromPaddings(enc_paddings), targets.ids.long(),
+        py_utils.LengthsFromPaddings(targets.paddings),
+        blank_id=p.blank_id, impl=p.align_impl)
+    return NestedMap(al._asdict())
 
   def GreedyDecode(self, theta: NestedMap, enc: torch.Tensor,
                    enc_paddings: torch.Tensor, max_len: int = 0,
@@ -805,8 +824,35 @@ class AsrModel(BaseTask):
     return NestedMap(topk_decoded=hyps,
                      transcripts=input_batch.tgt.ids)
 
+  def _CtcHead(self):
+    """(layer, theta) of the CTC head that can align, or None: the decoder
+    if it is one, else the auxiliary head of joint training."""
+    if hasattr(self.decoder, 'Align'):
+      return self.decoder, self.theta.decoder
+    if self.p.ctc_weight > 0:
+      return self.aux_ctc, self.theta.aux_ctc
+    return None
+
+  def _Align(self, src_inputs, paddings, targets: NestedMap) -> NestedMap:
+    head = self._CtcHead()
+    if head is None:
+      raise ValueError(
+          'AsrModel.Align needs a CTC head: a CtcDecoder as the decoder, or '
+          'ctc_weight > 0 for an auxiliary one (aux_ctc)')
+    with torch.no_grad():
+      enc, enc_pad = self.encoder.FProp(self.theta.encoder, src_inputs,
+                                        paddings)
+      return head[0].Align(head[1], enc, enc_pad, targets)
+
+  def Align(self, input_batch: NestedMap) -> NestedMap:
+    """Forced alignment of input_batch.tgt to the encoder frames; see
+    CtcDecoder.Align."""
+    return self._Align(input_batch.src.src_inputs, input_batch.src.paddings,
+                       input_batch.tgt)
+
   def Inference(self) -> NestedMap:
-    """Named inference subgraphs (reference base_model.py:943)."""
+    """Named inference subgraphs (reference base_model.py:943). `align` is
+    there only when the model has a CTC head."""
 
     def default(src_inputs, paddings):
       enc, enc_pad = self.encoder.FProp(self.theta.encoder,
@@ -819,7 +865,14 @@ class AsrModel(BaseTask):
                                         src_inputs, paddings)
       return NestedMap(encoded=enc, padding=enc_pad)
 
-    return NestedMap(default=default, encode=encode)
+    def align(src_inputs, paddings, tgt_ids, tgt_paddings):
+      return self._Align(src_inputs, paddings,
+                         NestedMap(ids=tgt_ids, paddings=tgt_paddings))
+
+    subgraphs = NestedMap(default=default, encode=encode)
+    if self._CtcHead() is not None:
+      subgraphs.align = align
+    return subgraphs
 
   def CreateDecoderMetrics(self) -> NestedMap:
     return NestedMap(wer=metrics_lib.WerMetric(),

@@ -16,9 +16,36 @@ no fp32 [B,T,V] intermediate, deterministic backward). CPU tensors run a
 torch twin of the same recursion in the dtype of the input (fp32 or
 fp64). impl='torch' routes to torch.nn.functional.ctc_loss on either
 device: the yardstick for tests and benchmarks.
+
+  al = ctc_forced_align(logits, logit_lengths, labels, label_lengths,
+                        blank_id=0, impl='auto')
+
+is the best single alignment of each transcript (Viterbi) under the same
+inputs, checks and validity rules, as a CtcAlignment:
+  frame_ids   [B,T] int64  the label (or blank_id) each frame is aligned to
+  token_start [B,L] int64  first frame of each label
+  token_end   [B,L] int64  one past its last frame
+  token_logp  [B,L]        sum of its frames' log-probs
+  score       [B]          log-prob of the whole path
+  valid       [B]          1 or 0
+Units are frames of `logits`. Among predecessors of equal value the
+smallest jump wins (stay, then step, then skip), and of the two end
+positions the last label wins a tie with the final blank. Frames >= T_b
+get frame_ids -1, label slots >= L_b get spans -1 and token_logp 0, and an
+invalid row - the rules above, or a best score that is not possible - gets
+all of those and score 0. No output carries a gradient; logits that
+require one are detached.
+
+CUDA tensors run ctc_rows_kernel and ctc_viterbi_kernel of ops/hip/ctc.hip
+(two launches, no host sync, fp32 score and token_logp). CPU tensors run
+a batched torch twin of that recursion in the dtype of the input;
+impl='torch' runs the twin on whichever device the inputs are on: the
+composed-ops yardstick for the benchmark.
 """
 
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -72,6 +99,17 @@ def _ShiftLeft(x, n):
   return torch.cat([x[:, n:], torch.full_like(x[:, :n], _NEG)], dim=1)
 
 
+def _Emissions(logits, safe, blank_id):
+  """(log-probs [B,T,V], extended labels [B,S], emissions [B,T,S]) of the
+  blank-interleaved label sequence, S = 2L+1."""
+  b, t, _ = logits.shape
+  s = 2 * safe.shape[1] + 1
+  lp = F.log_softmax(logits, dim=-1)
+  ext = torch.full((b, s), blank_id, dtype=torch.long, device=logits.device)
+  ext[:, 1::2] = safe
+  return lp, ext, lp.gather(2, ext[:, None, :].expand(b, t, s))
+
+
 def _TwinForward(logits, logit_lengths, labels, label_lengths, blank_id):
   """The kernels' recursion in torch ops, batched over B, in
   logits.dtype. Returns nll, valid and what the backward needs."""
@@ -81,10 +119,7 @@ def _TwinForward(logits, logit_lengths, labels, label_lengths, blank_id):
   dev = logits.device
   valid, tb, lb, safe = _Validity(logit_lengths, labels, label_lengths, t, v,
                                   blank_id)
-  lp = F.log_softmax(logits, dim=-1)
-  ext = torch.full((b, s), blank_id, dtype=torch.long, device=dev)
-  ext[:, 1::2] = safe
-  emis = lp.gather(2, ext[:, None, :].expand(b, t, s))  # [B,T,S]
+  lp, ext, emis = _Emissions(logits, safe, blank_id)
   pos = torch.arange(s, device=dev)[None, :]
   sb = 2 * lb[:, None] + 1
   active = pos < sb
@@ -203,36 +238,37 @@ def _TorchCtc(logits, logit_lengths, labels, label_lengths, blank_id):
   return nll * valid, valid
 
 
-def _CheckArgs(logits, logit_lengths, labels, label_lengths, blank_id):
+def _CheckArgs(logits, logit_lengths, labels, label_lengths, blank_id,
+               fn='ctc_loss'):
   if logits.dim() != 3:
-    raise ValueError(f'ctc_loss: logits must be [B,T,V], got '
+    raise ValueError(f'{fn}: logits must be [B,T,V], got '
                      f'{tuple(logits.shape)}')
   if not logits.is_floating_point():
-    raise TypeError(f'ctc_loss: logits must be floating point, got '
+    raise TypeError(f'{fn}: logits must be floating point, got '
                     f'{logits.dtype}')
   if not logits.is_contiguous():
-    raise ValueError('ctc_loss: logits must be contiguous')
+    raise ValueError(f'{fn}: logits must be contiguous')
   b, t, v = logits.shape
   if b < 1 or t < 1:
-    raise ValueError('ctc_loss: B >= 1 and T >= 1')
+    raise ValueError(f'{fn}: B >= 1 and T >= 1')
   if v < 2:
-    raise ValueError('ctc_loss: V >= 2')
+    raise ValueError(f'{fn}: V >= 2')
   if not 0 <= blank_id < v:
-    raise ValueError(f'ctc_loss: blank_id {blank_id} outside [0, {v})')
+    raise ValueError(f'{fn}: blank_id {blank_id} outside [0, {v})')
   if labels.dtype != torch.int64 or labels.dim() != 2 or \
       labels.shape[0] != b:
-    raise TypeError('ctc_loss: labels must be int64 [B,L]')
+    raise TypeError(f'{fn}: labels must be int64 [B,L]')
   if labels.shape[1] > MAX_LABEL_LEN:
-    raise ValueError(f'ctc_loss: L={labels.shape[1]} is over the supported '
+    raise ValueError(f'{fn}: L={labels.shape[1]} is over the supported '
                      f'limit {MAX_LABEL_LEN}')
   for name, x in (('logit_lengths', logit_lengths),
                   ('label_lengths', label_lengths)):
     if x.dim() != 1 or x.shape[0] != b or x.is_floating_point() or \
         x.dtype == torch.bool:
-      raise TypeError(f'ctc_loss: {name} must be an integer tensor [B]')
+      raise TypeError(f'{fn}: {name} must be an integer tensor [B]')
   for x in (logit_lengths, labels, label_lengths):
     if x.device != logits.device:
-      raise ValueError('ctc_loss: all inputs must be on one device')
+      raise ValueError(f'{fn}: all inputs must be on one device')
 
 
 def ctc_loss(logits: torch.Tensor, logit_lengths: torch.Tensor,
@@ -253,3 +289,117 @@ def ctc_loss(logits: torch.Tensor, logit_lengths: torch.Tensor,
                     f'got {logits.dtype}')
   return _CtcLossFn.apply(logits, logit_lengths, labels, label_lengths,
                           blank_id)
+
+
+class CtcAlignment(NamedTuple):
+  """What ctc_forced_align returns; see the module docstring."""
+  frame_ids: torch.Tensor    # [B,T] int64
+  token_start: torch.Tensor  # [B,L] int64
+  token_end: torch.Tensor    # [B,L] int64
+  token_logp: torch.Tensor   # [B,L]
+  score: torch.Tensor        # [B]
+  valid: torch.Tensor        # [B]
+
+
+def _TwinAlign(logits, logit_lengths, labels, label_lengths, blank_id):
+  """ctc_viterbi_kernel's recursion in torch ops, batched over B, in
+  logits.dtype: max in place of logsumexp with a [B,T,S] int8 backpointer
+  tensor, then a backtrace of one gather per frame. No host sync."""
+  b, t, v = logits.shape
+  l = labels.shape[1]
+  s = 2 * l + 1
+  dev = logits.device
+  valid, tb, lb, safe = _Validity(logit_lengths, labels, label_lengths, t, v,
+                                  blank_id)
+  _, ext, emis = _Emissions(logits, safe, blank_id)
+  pos = torch.arange(s, device=dev)[None, :]
+  sb = 2 * lb[:, None] + 1
+  active = pos < sb
+  neg = torch.full((b, s), _NEG, dtype=logits.dtype, device=dev)
+  # A step of two positions is allowed only between different labels.
+  skip = torch.zeros(b, s, dtype=torch.bool, device=dev)
+  if s >= 3:
+    skip[:, 2:] = ((pos[:, 2:] % 2) == 1) & active[:, 2:] & \
+        (ext[:, 2:] != ext[:, :-2])
+
+  # Forward: which predecessor won (0 stay, 1 step, 2 skip); among equal
+  # values the smallest jump, so only a strictly larger value replaces.
+  a = torch.where((pos < 2) & active, emis[:, 0], neg)
+  bp = torch.zeros(b, t, s, dtype=torch.int8, device=dev)
+  for i in range(1, t):
+    m = a
+    mv = torch.zeros(b, s, dtype=torch.int8, device=dev)
+    for jump, cand in ((1, _ShiftRight(a, 1)),
+                       (2, torch.where(skip, _ShiftRight(a, 2), neg))):
+      take = cand > m
+      m = torch.where(take, cand, m)
+      mv = torch.where(take, torch.full_like(mv, jump), mv)
+    new = torch.where(active & (m > _NEG_TEST), emis[:, i] + m, neg)
+    live = (i < tb)[:, None]
+    a = torch.where(live, new, a)  # frozen past the end
+    bp[:, i] = torch.where(live, mv, torch.zeros_like(mv))
+  a1 = a.gather(1, (sb - 1).clamp(min=0))[:, 0]
+  a2 = torch.where(sb[:, 0] >= 2,
+                   a.gather(1, (sb - 2).clamp(min=0))[:, 0], neg[:, 0])
+  end_last = a1 >= a2  # the last position wins a tie
+  best = torch.where(end_last, a1, a2)
+  valid = valid & (best > _NEG_TEST)
+
+  # Backtrace: state [B,T] is the lattice position of each frame, -1 on
+  # padded frames and invalid rows.
+  cur = torch.where(end_last, sb[:, 0] - 1, sb[:, 0] - 2).clamp(min=0)
+  state = torch.full((b, t), -1, dtype=torch.long, device=dev)
+  for i in range(t - 1, -1, -1):
+    on = valid & (i < tb)
+    state[:, i] = torch.where(on, cur, torch.full_like(cur, -1))
+    mv = bp[:, i].gather(1, cur[:, None])[:, 0].long()
+    cur = torch.where(on, cur - mv, cur)
+  on = state >= 0
+  at = state.clamp(min=0)
+  frame_ids = torch.where(on, ext.gather(1, at), torch.full_like(at, -1))
+  logp = torch.where(on, emis.gather(2, at[:, :, None])[:, :, 0],
+                     torch.zeros_like(emis[:, :, 0]))
+  # Per label: first frame, one past the last frame, sum of log-probs.
+  # Frames on a blank go to a spare column l.
+  tok = torch.where(on & (at % 2 == 1), at // 2, torch.full_like(at, l))
+  frame = torch.arange(t, device=dev)[None, :].expand(b, t)
+  start = torch.full((b, l + 1), t, dtype=torch.long, device=dev)
+  start = start.scatter_reduce(1, tok, frame, 'amin')[:, :l]
+  end = torch.full((b, l + 1), -1, dtype=torch.long, device=dev)
+  end = end.scatter_reduce(1, tok, frame, 'amax')[:, :l] + 1
+  token_logp = torch.zeros(b, l + 1, dtype=logits.dtype, device=dev)
+  token_logp = token_logp.scatter_add(1, tok, logp)[:, :l]
+  used = valid[:, None] & \
+      (torch.arange(l, device=dev)[None, :] < lb[:, None])
+  return CtcAlignment(
+      frame_ids=frame_ids,
+      token_start=torch.where(used, start, torch.full_like(start, -1)),
+      token_end=torch.where(used, end, torch.full_like(end, -1)),
+      token_logp=torch.where(used, token_logp, torch.zeros_like(token_logp)),
+      score=torch.where(valid, best, torch.zeros_like(best)),
+      valid=valid.to(logits.dtype))
+
+
+def ctc_forced_align(logits: torch.Tensor, logit_lengths: torch.Tensor,
+                     labels: torch.Tensor, label_lengths: torch.Tensor,
+                     blank_id: int = 0, impl: str = 'auto') -> CtcAlignment:
+  """-> CtcAlignment of the best alignment; see the module docstring."""
+  fn = 'ctc_forced_align'
+  if impl not in ('auto', 'torch'):
+    raise ValueError(f"{fn}: impl must be 'auto' or 'torch', got {impl!r}")
+  blank_id = int(blank_id)
+  _CheckArgs(logits, logit_lengths, labels, label_lengths, blank_id, fn=fn)
+  logits = logits.detach()
+  logit_lengths = logit_lengths.long().contiguous()
+  label_lengths = label_lengths.long().contiguous()
+  labels = labels.contiguous()
+  if impl == 'auto' and logits.is_cuda:
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+      raise TypeError(f'{fn}: the HIP kernels take bf16 or fp32 logits, got '
+                      f'{logits.dtype}')
+    ext = _loader.get_ext(required=True)
+    # True: backpointer masks in LDS where all T frames fit.
+    return CtcAlignment(*ext.ctc_align(logits, logit_lengths, labels,
+                                       label_lengths, blank_id, True))
+  x = logits if logits.dtype == torch.float64 else logits.float()
+  return _TwinAlign(x, logit_lengths, labels, label_lengths, blank_id)

@@ -219,6 +219,11 @@ torch::Tensor ctc_bwd(torch::Tensor logits, torch::Tensor logit_lengths,
                       torch::Tensor nll, torch::Tensor valid,
                       torch::Tensor gout, int64_t blank);
 int64_t ctc_max_label_len();
+std::vector<torch::Tensor> ctc_align(torch::Tensor logits,
+                                     torch::Tensor logit_lengths,
+                                     torch::Tensor labels,
+                                     torch::Tensor label_lengths,
+                                     int64_t blank, bool lds_masks);
 
 // rnnt.hip
 std::vector<torch::Tensor> rnnt_fwd(torch::Tensor logits,
@@ -349,6 +354,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ctc_bwd", &ctc_bwd, "CTC loss backward: dlogits");
   m.def("ctc_max_label_len", &ctc_max_label_len,
         "Largest label width L the CTC kernels support");
+  m.def("ctc_align", &ctc_align,
+        "CTC forced alignment: frame ids, token spans and log-probs, score, "
+        "valid");
   m.def("rnnt_fwd", &rnnt_fwd,
         "Transducer loss forward: nll, valid and the backward's workspaces");
   m.def("rnnt_bwd", &rnnt_bwd, "Transducer loss backward: dlogits");

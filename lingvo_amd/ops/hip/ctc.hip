@@ -27,6 +27,10 @@
 // its likelihood is not finite. Labels are range-checked before every use
 // as an index, so an invalid row never reads or writes out of range.
 // Every element of every output and workspace is written.
+//
+// Forced alignment (ctc_align) is pass 1 followed by ctc_viterbi_kernel:
+// the best single alignment of each transcript instead of the sum over all
+// of them, with the same validity rules. See the comment at that kernel.
 
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
@@ -41,6 +45,9 @@ constexpr int kRowWaves = 4;    // rows per workgroup in the row pass
 constexpr int kGradThreads = 256;
 constexpr float kNeg = -1e30f;
 constexpr float kNegTest = -1e29f;
+// Dynamic LDS ctc_viterbi_kernel may take for its masks, next to 10 KB of
+// static LDS: together under the 64 KB a workgroup gets by default.
+constexpr int kLdsMaskBytes = 48 * 1024;
 
 // Lengths of utterance b, zeroed when either is out of range.
 __device__ __forceinline__ bool RowLengths(const long* in_len,
@@ -119,6 +126,25 @@ __device__ __forceinline__ float Lse3(float a, float b, float c) {
   return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
 }
 
+// Lattice prologue of utterance b, one lane per position s: labels into LDS
+// (range-checked), then whether the row has an alignment at all. Holds two
+// workgroup barriers, so every lane calls it; the result is uniform.
+__device__ __forceinline__ bool LabelsToLds(const long* __restrict__ labels,
+                                            int b, int s, int V, int L,
+                                            int blank, bool len_ok, int tb,
+                                            int lb, int* lab) {
+  int bad = 0, rep = 0;
+  if (s < lb) {  // blockDim.x >= S > L >= lb
+    const long v = labels[(long)b * L + s];
+    bad = (v < 0 || v >= V || v == blank) ? 1 : 0;
+    lab[s] = bad ? 0 : (int)v;
+    if (s > 0) rep = (labels[(long)b * L + s - 1] == v) ? 1 : 0;
+  }
+  const int nbad = __syncthreads_count(bad);
+  const int nrep = __syncthreads_count(rep);
+  return len_ok && nbad == 0 && tb >= lb + nrep;
+}
+
 __global__ void __launch_bounds__(1024)
     ctc_lattice_kernel(const float* __restrict__ emis,
                        const long* __restrict__ in_len,
@@ -136,17 +162,8 @@ __global__ void __launch_bounds__(1024)
   int tb, lb;
   const bool len_ok = RowLengths(in_len, lab_len, b, Tn, L, &tb, &lb);
 
-  // Labels into LDS (range-checked), bad-label and repeat counts.
-  int bad = 0, rep = 0;
-  if (s < lb) {  // blockDim.x >= S > L >= lb
-    const long v = labels[(long)b * L + s];
-    bad = (v < 0 || v >= V || v == blank) ? 1 : 0;
-    lab[s] = bad ? 0 : (int)v;
-    if (s > 0) rep = (labels[(long)b * L + s - 1] == v) ? 1 : 0;
-  }
-  const int nbad = __syncthreads_count(bad);
-  const int nrep = __syncthreads_count(rep);
-  const bool feasible = len_ok && nbad == 0 && tb >= lb + nrep;
+  const bool feasible =
+      LabelsToLds(labels, b, s, V, L, blank, len_ok, tb, lb, lab);
 
   float* out = (dir ? beta : alpha) + (long)b * Tn * S;
   if (!feasible) {  // uniform over the workgroup
@@ -213,6 +230,186 @@ __global__ void __launch_bounds__(1024)
     const bool ok = m > kNegTest && isfinite(ll);
     nll[b] = ok ? -ll : 0.f;
     valid[b] = ok ? 1.f : 0.f;
+  }
+}
+
+// ---- forced alignment: the best single path --------------------------------
+// The alpha workgroup of ctc_lattice_kernel with max in place of logsumexp:
+// one workgroup per utterance, one lane per position, the same prologue,
+// LDS buffers and one barrier per frame. Each lane records which
+// predecessor won (0 stay, 1 step, 2 skip; among equal values the smallest),
+// and a wave packs its 64 two-bit choices into two __ballot masks that lane
+// 0 stores as one 16-byte word pair: bp [B,T,W,2], W = waves per workgroup.
+//
+// After the loop thread 0 walks the masks back from the better of the two
+// end positions (the last one on a tie) and writes the frame ids, and for
+// every label its span [start, end) and the sum of its frames' log-probs.
+// The masks it reads were stored by other waves of this workgroup, the last
+// of them before the loop's final __syncthreads(). That barrier is a
+// workgroup-scope release and acquire, which is all the hand-off needs: the
+// waves of a workgroup run on one CU and share its write-through L1, which
+// serves their accesses in order, so a load issued after the barrier sees a
+// store issued before it; and no lane loaded these words before they were
+// stored, so no older copy of them exists. No other workgroup reads or
+// writes them in this launch. The same in-order path covers the one
+// store-after-store case: a feasible row whose best score turns out not to
+// be possible has the masks its loop stored overwritten with zeros by other
+// lanes after that barrier, and the later store lands last.
+//
+// A row without an alignment, or whose best score is not above kNegTest,
+// gets valid = 0, score = 0, frame_ids = -1, spans -1, token_logp = 0 and
+// zero masks. Frames >= T_b get frame_ids = -1 and zero masks, label slots
+// >= L_b get spans -1 and token_logp = 0.
+//
+// kLdsMasks keeps the masks in dynamic LDS, [Tn, W] word pairs, instead of
+// the global workspace (bp is then unused): the walk's chain of dependent
+// loads then runs at LDS latency. The host picks it when they fit.
+template <bool kLdsMasks>
+__global__ void __launch_bounds__(1024)
+    ctc_viterbi_kernel(const float* __restrict__ emis,
+                       const long* __restrict__ in_len,
+                       const long* __restrict__ labels,
+                       const long* __restrict__ lab_len, ulonglong2* bp,
+                       long* __restrict__ frame_ids,
+                       long* __restrict__ token_start,
+                       long* __restrict__ token_end,
+                       float* __restrict__ token_logp,
+                       float* __restrict__ score, float* __restrict__ valid,
+                       int Tn, int V, int L, int blank) {
+  __shared__ int lab[kCtcMaxL + 1];
+  __shared__ float buf[2][1024];
+  extern __shared__ ulonglong2 lds_masks[];
+  const int b = blockIdx.x;
+  const int s = threadIdx.x;
+  const int lane = s & (WAVE_SIZE - 1);
+  const int wave = s / WAVE_SIZE;
+  const int W = blockDim.x / WAVE_SIZE;
+  int tb, lb;
+  const bool len_ok = RowLengths(in_len, lab_len, b, Tn, L, &tb, &lb);
+  const bool feasible =
+      LabelsToLds(labels, b, s, V, L, blank, len_ok, tb, lb, lab);
+
+  // [Tn, W] word pairs of this utterance.
+  ulonglong2* bpw = kLdsMasks ? lds_masks : bp + (long)b * Tn * W;
+  long* fid = frame_ids + (long)b * Tn;
+  long* ts = token_start + (long)b * L;
+  long* te = token_end + (long)b * L;
+  float* tl = token_logp + (long)b * L;
+  const ulonglong2 zero2 = make_ulonglong2(0ull, 0ull);
+
+  float best = kNeg;
+  bool end_last = true;
+  const int sb = 2 * lb + 1;
+  if (feasible) {  // uniform over the workgroup
+    const bool active = s < sb;
+    const bool odd = (s & 1) != 0;
+    const bool has1 = active && s >= 1;
+    const bool skip =
+        active && odd && s >= 3 && lab[(s - 1) / 2] != lab[(s - 3) / 2];
+    const float* eb = emis + (long)b * Tn * (L + 1) + (odd ? (s + 1) / 2 : 0);
+    float e_cur = active ? eb[0] : 0.f;
+    for (int t = 0; t < tb; ++t) {
+      float e_next = 0.f;
+      if (active && t + 1 < tb) e_next = eb[(long)(t + 1) * (L + 1)];
+      float v = kNeg;
+      int mv = 0;
+      if (active) {
+        if (t == 0) {
+          v = s < 2 ? e_cur : kNeg;
+        } else {
+          const float* prev = buf[(t - 1) & 1];
+          float m = prev[s];
+          if (has1) {
+            const float p1 = prev[s - 1];
+            if (p1 > m) {
+              m = p1;
+              mv = 1;
+            }
+          }
+          if (skip) {
+            const float p2 = prev[s - 2];
+            if (p2 > m) {
+              m = p2;
+              mv = 2;
+            }
+          }
+          v = m > kNegTest ? e_cur + m : kNeg;
+        }
+      }
+      buf[t & 1][s] = v;
+      const unsigned long long m0 = __ballot(mv & 1);
+      const unsigned long long m1 = __ballot(mv >> 1);
+      if (lane == 0) bpw[(long)t * W + wave] = make_ulonglong2(m0, m1);
+      e_cur = e_next;
+      __syncthreads();
+    }
+    const float* last = buf[(tb - 1) & 1];
+    const float a1 = last[sb - 1];
+    const float a2 = sb >= 2 ? last[sb - 2] : kNeg;
+    end_last = a1 >= a2;
+    best = end_last ? a1 : a2;
+  }
+
+  if (!(best > kNegTest)) {  // uniform: no alignment
+    if (!kLdsMasks)
+      for (long i = s; i < (long)Tn * W; i += blockDim.x) bpw[i] = zero2;
+    for (int t = s; t < Tn; t += blockDim.x) fid[t] = -1;
+    for (int j = s; j < L; j += blockDim.x) {
+      ts[j] = -1;
+      te[j] = -1;
+      tl[j] = 0.f;
+    }
+    if (s == 0) {
+      score[b] = 0.f;
+      valid[b] = 0.f;
+    }
+    return;
+  }
+
+  // Frames past the utterance's end and unused label slots.
+  if (!kLdsMasks)
+    for (long i = (long)tb * W + s; i < (long)Tn * W; i += blockDim.x)
+      bpw[i] = zero2;
+  for (int t = tb + s; t < Tn; t += blockDim.x) fid[t] = -1;
+  for (int j = lb + s; j < L; j += blockDim.x) {
+    ts[j] = -1;
+    te[j] = -1;
+    tl[j] = 0.f;
+  }
+  if (s != 0) return;
+
+  // Backtrace. Every label position of a path from {0,1} to {sb-2,sb-1} is
+  // visited, so every slot j < lb is stored exactly once.
+  score[b] = best;
+  valid[b] = 1.f;
+  const float* er = emis + (long)b * Tn * (L + 1);
+  int sc = end_last ? sb - 1 : sb - 2;
+  int end = 0;
+  float acc = 0.f;
+  bool open = false;
+  for (int t = tb - 1; t >= 0; --t) {
+    const ulonglong2 w = bpw[(long)t * W + sc / WAVE_SIZE];
+    const int bit = sc & (WAVE_SIZE - 1);
+    const int mv = (int)((w.x >> bit) & 1) | ((int)((w.y >> bit) & 1) << 1);
+    const int j = sc >> 1;  // label index of an odd position
+    if (sc & 1) {
+      fid[t] = lab[j];
+      if (!open) {
+        open = true;
+        end = t + 1;
+        acc = 0.f;
+      }
+      acc += er[(long)t * (L + 1) + j + 1];
+      if (mv != 0 || t == 0) {  // leaving the label (frame 0 has no move)
+        ts[j] = t;
+        te[j] = end;
+        tl[j] = acc;
+        open = false;
+      }
+    } else {
+      fid[t] = blank;
+    }
+    sc = max(sc - mv, 0);  // in range whatever the words hold
   }
 }
 
@@ -364,6 +561,34 @@ void CheckF32(const torch::Tensor& x, std::vector<int64_t> shape,
               "ctc_fwd returned");
 }
 
+// Pass 1 on `stream`: lse [B,T] and emis [B,T,L+1].
+void LaunchRows(const torch::Tensor& logits,
+                const torch::Tensor& logit_lengths,
+                const torch::Tensor& labels,
+                const torch::Tensor& label_lengths, torch::Tensor& lse,
+                torch::Tensor& emis, const CtcShape& sh, int64_t blank,
+                hipStream_t stream) {
+  const long rows = (long)sh.B * sh.T;
+  const dim3 rgrid(cdiv(rows, kRowWaves)), rblock(kRowWaves * WAVE_SIZE);
+  if (logits.scalar_type() == torch::kBFloat16) {
+    hipLaunchKernelGGL(ctc_rows_kernel<unsigned short>, rgrid, rblock, 0,
+                       stream, (const unsigned short*)logits.data_ptr(),
+                       logit_lengths.data_ptr<long>(),
+                       labels.data_ptr<long>(),
+                       label_lengths.data_ptr<long>(), lse.data_ptr<float>(),
+                       emis.data_ptr<float>(), sh.B, sh.T, sh.V, sh.L,
+                       (int)blank);
+  } else {
+    hipLaunchKernelGGL(ctc_rows_kernel<float>, rgrid, rblock, 0, stream,
+                       logits.data_ptr<float>(),
+                       logit_lengths.data_ptr<long>(),
+                       labels.data_ptr<long>(),
+                       label_lengths.data_ptr<long>(), lse.data_ptr<float>(),
+                       emis.data_ptr<float>(), sh.B, sh.T, sh.V, sh.L,
+                       (int)blank);
+  }
+}
+
 }  // namespace
 
 int64_t ctc_max_label_len() { return kCtcMaxL; }
@@ -385,23 +610,8 @@ std::vector<torch::Tensor> ctc_fwd(torch::Tensor logits,
   auto alpha = torch::empty({B, T, S}, opts);
   auto beta = torch::empty({B, T, S}, opts);
   auto stream = at::cuda::getCurrentCUDAStream();
-  const long rows = (long)B * T;
-  const dim3 rgrid(cdiv(rows, kRowWaves)), rblock(kRowWaves * WAVE_SIZE);
-  if (logits.scalar_type() == torch::kBFloat16) {
-    hipLaunchKernelGGL(ctc_rows_kernel<unsigned short>, rgrid, rblock, 0,
-                       stream, (const unsigned short*)logits.data_ptr(),
-                       logit_lengths.data_ptr<long>(),
-                       labels.data_ptr<long>(),
-                       label_lengths.data_ptr<long>(), lse.data_ptr<float>(),
-                       emis.data_ptr<float>(), B, T, V, L, (int)blank);
-  } else {
-    hipLaunchKernelGGL(ctc_rows_kernel<float>, rgrid, rblock, 0, stream,
-                       logits.data_ptr<float>(),
-                       logit_lengths.data_ptr<long>(),
-                       labels.data_ptr<long>(),
-                       label_lengths.data_ptr<long>(), lse.data_ptr<float>(),
-                       emis.data_ptr<float>(), B, T, V, L, (int)blank);
-  }
+  LaunchRows(logits, logit_lengths, labels, label_lengths, lse, emis, sh,
+             blank, stream);
   const int threads = cdiv(S, WAVE_SIZE) * WAVE_SIZE;  // <= 1024
   hipLaunchKernelGGL(ctc_lattice_kernel, dim3(B, 2), dim3(threads), 0, stream,
                      emis.data_ptr<float>(), logit_lengths.data_ptr<long>(),
@@ -453,4 +663,48 @@ torch::Tensor ctc_bwd(torch::Tensor logits, torch::Tensor logit_lengths,
         (int)blank);
   }
   return dlogits;
+}
+
+// -> {frame_ids [B,T] i64, token_start, token_end [B,L] i64,
+//     token_logp [B,L], score [B], valid [B]}. lds_masks = false keeps the
+// backpointer masks in the global workspace whatever the shape.
+std::vector<torch::Tensor> ctc_align(torch::Tensor logits,
+                                     torch::Tensor logit_lengths,
+                                     torch::Tensor labels,
+                                     torch::Tensor label_lengths,
+                                     int64_t blank, bool lds_masks) {
+  const CtcShape sh =
+      CheckCtcInputs(logits, logit_lengths, labels, label_lengths, blank);
+  const int B = sh.B, T = sh.T, L = sh.L, S = 2 * sh.L + 1;
+  const int waves = cdiv(S, WAVE_SIZE);  // <= 16
+  // Masks in LDS when the caller allows it and all T frames fit.
+  const long mask_bytes = (long)T * waves * sizeof(ulonglong2);
+  const bool in_lds = lds_masks && mask_bytes <= kLdsMaskBytes;
+  auto f32 = logits.options().dtype(torch::kFloat32);
+  auto i64 = logits.options().dtype(torch::kInt64);
+  auto lse = torch::empty({B, T}, f32);
+  auto emis = torch::empty({B, T, L + 1}, f32);
+  auto bp = torch::empty({in_lds ? 0 : B, T, waves, 2}, i64);
+  auto frame_ids = torch::empty({B, T}, i64);
+  auto token_start = torch::empty({B, L}, i64);
+  auto token_end = torch::empty({B, L}, i64);
+  auto token_logp = torch::empty({B, L}, f32);
+  auto score = torch::empty({B}, f32);
+  auto valid = torch::empty({B}, f32);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  LaunchRows(logits, logit_lengths, labels, label_lengths, lse, emis, sh,
+             blank, stream);
+  hipLaunchKernelGGL(in_lds ? ctc_viterbi_kernel<true>
+                            : ctc_viterbi_kernel<false>,
+                     dim3(B), dim3(waves * WAVE_SIZE),
+                     in_lds ? (size_t)mask_bytes : 0, stream,
+                     emis.data_ptr<float>(),
+                     logit_lengths.data_ptr<long>(), labels.data_ptr<long>(),
+                     label_lengths.data_ptr<long>(),
+                     reinterpret_cast<ulonglong2*>(bp.data_ptr()),
+                     frame_ids.data_ptr<long>(), token_start.data_ptr<long>(),
+                     token_end.data_ptr<long>(),
+                     token_logp.data_ptr<float>(), score.data_ptr<float>(),
+                     valid.data_ptr<float>(), T, sh.V, L, (int)blank);
+  return {frame_ids, token_start, token_end, token_logp, score, valid};
 }
