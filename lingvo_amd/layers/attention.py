@@ -21,6 +21,7 @@ from lingvo_amd.core.base_layer import BaseLayer
 from lingvo_amd.core.nested_map import NestedMap
 from lingvo_amd.ops import attn_decode
 from lingvo_amd.ops import flash_attn
+from lingvo_amd.ops import xl_attn
 
 
 class MultiHeadedAttention(BaseLayer):
@@ -263,16 +264,25 @@ class TransformerXLAttention(MultiHeadedAttention):
   with learned per-head biases u, v and sinusoidal relative embeddings
   r projected per head. `memory` (the previous segment's input hidden
   states, no grad) is prepended on the key/value side, giving XL-style
-  segment recurrence. This composed-einsum form runs on CPU and GPU but
-  materializes the [B, N, T, L] rel-logits; the in-kernel rel-shift
-  variant (extra MFMA against a staged R tile) is a round-3 item
-  (docs/ROADMAP.md #6).
+  segment recurrence.
+
+  Two routes, chosen by `xl_impl` and the projected tensors: bf16 CUDA
+  tensors with dim_per_head 64 under xl_impl='auto' run the gfx950 kernels
+  of ops/xl_attn.py (the rel-shift happens in registers against a staged
+  window of r; no [T, S] or [T, L] tensor exists forward or backward, and
+  pos_proj gets its gradient through the kernels' dr). Everything else -
+  CPU, other head dims or dtypes, xl_impl='torch' - runs the composed
+  einsum form, which materializes the [B, N, T, L] rel-logits.
   """
 
   @classmethod
   def Params(cls):
     p = super().Params()
     p.Define('max_rel_dist', 512, 'Max relative distance embedded.')
+    p.Define('xl_impl', 'auto',
+             "Attention-core route: 'auto' (HIP kernels on bf16 CUDA with "
+             "dim_per_head 64, composed torch elsewhere) or 'torch' (always "
+             "composed).")
     p.cls = cls
     return p
 
@@ -281,6 +291,7 @@ class TransformerXLAttention(MultiHeadedAttention):
     p = self.p
     n, h = self._n, self._h
     assert self._nkv == n, 'XL attention uses full KV heads'
+    assert p.xl_impl in ('auto', 'torch'), p.xl_impl
     self.CreateVariable('u_var', py_utils.WeightParams(
         [n, h], py_utils.WeightInit.Constant(0.0), p.dtype))
     self.CreateVariable('v_var', py_utils.WeightParams(
@@ -315,9 +326,40 @@ class TransformerXLAttention(MultiHeadedAttention):
         [memory.detach(), query_vec], dim=1)
     q, _, _ = self._Project(theta, query_vec)
     _, k, v = self._Project(theta, kv_in)
-    qf, kf, vf = q.float(), k.float(), v.float()
-    u = theta.u_var.float()[None, None]   # [1,1,N,H]
-    vv = theta.v_var.float()[None, None]
+    if (p.xl_impl == 'auto' and q.is_cuda and q.dtype == torch.bfloat16 and
+        h == xl_attn.KERNEL_HEAD_DIM):
+      ctx = self._KernelContext(theta, q, k, v, paddings, m)
+    else:
+      ctx = self._ComposedContext(theta, q, k, v, paddings, m)
+    ctx = ctx.reshape(b, t, n * h).to(query_vec.dtype)
+    post = py_utils.MatmulBias(ctx, theta.post_w,
+                               theta.post_b if p.use_bias else None)
+    if paddings is not None:
+      post = py_utils.ApplyPadding(paddings, post)
+    return post
+
+  def _KernelContext(self, theta, q, k, v, paddings, m):
+    """[B,T,N,H] context vectors from ops/xl_attn.py."""
+    s = k.shape[1]
+    uniq = torch.arange(-s + 1, s, device=q.device)
+    r = self._RelEmb(uniq, theta).to(q.dtype)              # [2S-1,N,H]
+    klen = None
+    if paddings is not None:
+      klen = (m + py_utils.LengthsFromPaddings(paddings)).to(torch.int32)
+    return xl_attn.xl_attention(q, k, v, r, theta.u_var, theta.v_var,
+                                klen=klen, causal=self.p.causal)
+
+  def _ComposedContext(self, theta, q, k, v, paddings, m):
+    """[B,T,N,H] context vectors from composed einsums in fp32 (fp64 for
+    fp64 inputs)."""
+    p = self.p
+    n, h = self._n, self._h
+    b, t = q.shape[0], q.shape[1]
+    memory = m > 0
+    ft = torch.float64 if q.dtype == torch.float64 else torch.float32
+    qf, kf, vf = q.to(ft), k.to(ft), v.to(ft)
+    u = theta.u_var.to(ft)[None, None]   # [1,1,N,H]
+    vv = theta.v_var.to(ft)[None, None]
     scale = 1.0 / math.sqrt(h)
     ac = torch.einsum('btnh,bsnh->bnts', qf + u, kf)
     # distances d(i, j) = (m + i) - j for key index j in [0, m+t)
@@ -325,7 +367,7 @@ class TransformerXLAttention(MultiHeadedAttention):
     kpos = torch.arange(m + t, device=q.device)
     dmat = qpos[:, None] - kpos[None, :]                   # [T, S]
     uniq = torch.arange(-(m + t) + 1, m + t, device=q.device)
-    r = self._RelEmb(uniq, theta).float()                  # [L,N,H]
+    r = self._RelEmb(uniq, theta).to(ft)                   # [L,N,H]
     bd_all = torch.einsum('btnh,lnh->bntl', qf + vv, r)
     idx = (dmat + (m + t) - 1).reshape(-1)
     bd = bd_all.reshape(b, n, t, -1).gather(
@@ -335,15 +377,9 @@ class TransformerXLAttention(MultiHeadedAttention):
         torch.ones(t, m + t, dtype=torch.bool, device=q.device)
     mask = mask[None, None].expand(b, 1, t, m + t).clone()
     if paddings is not None:
-      kpad = paddings if memory is None else torch.cat(
+      kpad = paddings if not memory else torch.cat(
           [torch.zeros(b, m, device=q.device), paddings], dim=1)
       mask = mask & (kpad[:, None, None, :] < 0.5)
     logits = logits.masked_fill(~mask, -1e30)
     probs = torch.softmax(logits, dim=-1)
-    ctx = torch.einsum('bnts,bsnh->btnh', probs, vf)
-    ctx = ctx.reshape(b, t, n * h).to(query_vec.dtype)
-    post = py_utils.MatmulBias(ctx, theta.post_w,
-                               theta.post_b if p.use_bias else None)
-    if paddings is not None:
-      post = py_utils.ApplyPadding(paddings, post)
-    return post
+    return torch.einsum('bnts,bsnh->btnh', probs, vf)

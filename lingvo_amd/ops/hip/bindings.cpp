@@ -225,6 +225,20 @@ std::vector<torch::Tensor> ctc_align(torch::Tensor logits,
                                      torch::Tensor label_lengths,
                                      int64_t blank, bool lds_masks);
 
+// xl_attn.hip
+std::vector<torch::Tensor> xl_attn_fwd(torch::Tensor q, torch::Tensor k,
+                                       torch::Tensor v, torch::Tensor r,
+                                       torch::Tensor u, torch::Tensor w,
+                                       c10::optional<torch::Tensor> klen,
+                                       bool causal, double scale);
+std::vector<torch::Tensor> xl_attn_bwd(torch::Tensor dout, torch::Tensor q,
+                                       torch::Tensor k, torch::Tensor v,
+                                       torch::Tensor r, torch::Tensor u,
+                                       torch::Tensor w, torch::Tensor o,
+                                       torch::Tensor lse,
+                                       c10::optional<torch::Tensor> klen,
+                                       bool causal, double scale);
+
 // rnnt.hip
 std::vector<torch::Tensor> rnnt_fwd(torch::Tensor logits,
                                     torch::Tensor logit_lengths,
@@ -357,6 +371,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ctc_align", &ctc_align,
         "CTC forced alignment: frame ids, token spans and log-probs, score, "
         "valid");
+  m.def("xl_attn_fwd", &xl_attn_fwd,
+        "Transformer-XL relative attention forward: o, lse");
+  m.def("xl_attn_bwd", &xl_attn_bwd,
+        "Transformer-XL relative attention backward: dq, dk, dv, dr, du, dw");
   m.def("rnnt_fwd", &rnnt_fwd,
         "Transducer loss forward: nll, valid and the backward's workspaces");
   m.def("rnnt_bwd", &rnnt_bwd, "Transducer loss backward: dlogits");
