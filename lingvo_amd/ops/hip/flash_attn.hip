@@ -4,10 +4,11 @@
 // relative-position bias, GQA).
 //
 // Structure (v1, correctness-first; guide §B "fused attention prefill"):
-//  - fwd: grid (ceil(T/64), N, B); block = 4 waves; each wave owns a
-//    16-row Q strip. K staged in LDS row-major (XOR-swizzled), V staged
-//    transposed [H][64]; online softmax in fp32 with per-row (m, l)
-//    tracked in the 16-lane C-layout groups; P routed through per-wave
+//  - fwd: grid (ceil(T/128), N, B); block = 8 waves; each wave owns a
+//    16-row Q strip. K staged in LDS row-major (XOR-swizzled) in tiles of
+//    64 keys (128 from S = 512 on), V staged transposed [H][tile]; online
+//    softmax in fp32 with per-row (m, l) tracked in the 16-lane C-layout
+//    groups; P routed through per-wave
 //    LDS for the PV MFMA. Saves LSE for backward.
 //  - bwd, two routes chosen on the host from shapes only:
 //    'fused' (fa_bwd_fused_kernel): self-attention with N == NKV, H == 64,
@@ -20,7 +21,7 @@
 //    stored as bf16; the bias gradient leaves as one fp32 row per
 //    workgroup, summed over B by fa_dbias_reduce. No atomics, no fp32 dQ
 //    buffer, fixed summation order.
-//    'tiles' (fa_bwd_delta + fa_bwd_kernel + fa_dq_cast): every other
+//    'tiles' (attn_delta_kernel + fa_bwd_kernel + fa_dq_cast): every other
 //    shape. Grid (ceil(S/128), N_kv, B), 8 waves; each block owns a
 //    128-key tile, loops q-heads of the GQA group and 64-row q-tiles;
 //    recomputes P^T from LSE; dK/dV in registers (written once; fp32
@@ -37,15 +38,9 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 
-#include "mfma.h"
+#include "attn_tile.h"
 
 namespace {
-
-constexpr int QT = 64;   // q rows per block (fwd) / q rows per inner tile (bwd)
-constexpr int KT = 64;   // keys per tile
-constexpr int NW = 4;    // waves per block
-constexpr int BLOCK = NW * WAVE_SIZE;
-constexpr float NEG_INF = -1e30f;
 
 // ---------------------------------------------------------------------------
 // LDS staging helpers. Row-major tiles are stored with a per-row XOR
@@ -55,7 +50,7 @@ constexpr float NEG_INF = -1e30f;
 
 // Stage ROWS x H bf16 from global (row i at src + i*src_stride elems) into
 // LDS row-major with swizzle. Rows >= valid_rows are zeroed.
-template <int H, int ROWS, int NT = BLOCK>
+template <int H, int ROWS, int NT>
 __device__ void stage_regular(const unsigned short* src, long src_stride,
                               int valid_rows, char* dst) {
   constexpr int ROWB = H * 2;
@@ -82,7 +77,7 @@ __device__ void stage_regular(const unsigned short* src, long src_stride,
 
 // Stage ROWS x H bf16 from global into LDS TRANSPOSED as [H][ROWS]
 // (ROWS=64, 128B rows), swizzled per h-row. Scalar 2B writes.
-template <int H, int ROWS, int NT = BLOCK, int PITCHB = ROWS * 2>
+template <int H, int ROWS, int NT, int PITCHB = ROWS * 2>
 __device__ void stage_transposed(const unsigned short* src, long src_stride,
                                  int valid_rows, char* dst) {
   // PITCHB must be >= 128 when the swizzle is in play: swz() XORs up to
@@ -111,18 +106,6 @@ __device__ void stage_transposed(const unsigned short* src, long src_stride,
           dst + h * PITCHB + swz(h, row * 2)) = v[j];
     }
   }
-}
-
-// ds_read a B-fragment (8 bf16) from a swizzled row-major LDS tile.
-__device__ __forceinline__ bf16x8 lds_frag(const char* tile, int row,
-                                           int rowb, int byte_in_row) {
-  union {
-    ushortx8 u;
-    bf16x8 h;
-  } cv;
-  cv.u = *reinterpret_cast<const ushortx8*>(tile + row * rowb +
-                                            swz(row, byte_in_row));
-  return cv.h;
 }
 
 __device__ __forceinline__ bool visible(int q, int k, int klen, int win_l,
@@ -384,43 +367,28 @@ __global__ __launch_bounds__(FWD_BLOCK) void fa_fwd_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Backward: delta = rowsum(dO * O)
-// ---------------------------------------------------------------------------
-template <int H>
-__global__ __launch_bounds__(BLOCK) void fa_bwd_delta(
-    const unsigned short* __restrict__ dout,
-    const unsigned short* __restrict__ o, float* __restrict__ delta, int B,
-    int T, int N) {
-  // H/8 neighbouring lanes per (b, t, n) row, one 16-byte load of dO and
-  // of O each; rows enumerate [B,T,N,H] in memory order.
-  constexpr int LPR = H / 8;           // lanes per row
-  constexpr int RPB = BLOCK / LPR;     // rows per block
-  const long nrows = (long)B * T * N;
-  const long row = (long)blockIdx.x * RPB + threadIdx.x / LPR;
-  const int c = threadIdx.x % LPR;
-  // Clamped row: whole waves stay in the shuffles below.
-  const long lrow = row < nrows ? row : nrows - 1;
-  const ushortx8 dv8 =
-      *reinterpret_cast<const ushortx8*>(dout + lrow * H + c * 8);
-  const ushortx8 ov8 = *reinterpret_cast<const ushortx8*>(o + lrow * H + c * 8);
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    sum += bf16_bits_to_float(dv8[j]) * bf16_bits_to_float(ov8[j]);
-#pragma unroll
-  for (int off = 1; off < LPR; off <<= 1) sum += __shfl_xor(sum, off);
-  if (c == 0 && row < nrows) {
-    long b = row / ((long)T * N);
-    long tn = row % ((long)T * N);
-    long t = tn / N, n = tn % N;
-    delta[(b * N + n) * T + t] = sum;
-  }
-}
-
-// ---------------------------------------------------------------------------
 // Backward main
 // ---------------------------------------------------------------------------
-template <int H, bool BIAS_GRAD, int KTB, int NWB, int QTB>
+// 128-key tiles with 8 waves (q-tile staging amortized 2x). H=128
+// uses 144KB LDS -> 1 block/CU; staging savings outweigh occupancy.
+constexpr int KTB = 128;
+constexpr int NWB = 8;
+// q-tile 64. A 32-row variant (2 blocks/CU via ~64 KB LDS) measured
+// SLOWER (bwd 0.73 -> 0.81 ms at the bench shape): doubled staging
+// sync passes outweigh the occupancy gain.
+constexpr int QTB = 64;
+
+// Dynamic LDS bytes of fa_bwd_kernel.
+static size_t bwd_lds_bytes(int H, bool bias_grad, int nbias) {
+  return (size_t)QTB * H * 2 * 2     // q_lds + do_lds
+         + (size_t)H * 128 * 2       // qt_lds + dot_lds (128B pitch)
+         + (size_t)H * KTB * 2       // kt_lds
+         + (size_t)QTB * KTB * 2     // ds_lds
+         + (size_t)NWB * 16 * 128    // a_lds (128B pitch)
+         + 2 * QTB * sizeof(float) + (bias_grad ? nbias * sizeof(float) : 0);
+}
+
+template <int H, bool BIAS_GRAD>
 __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
     const unsigned short* __restrict__ dout,
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
@@ -431,8 +399,7 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
     float* __restrict__ dq_acc,
     unsigned short* __restrict__ dk, unsigned short* __restrict__ dv,
     float* __restrict__ dbias, int B, int T, int S, int N, int NKV,
-    int win_l, int win_r, int bias_clip, float scale, int skip,
-    int chunk, int lc,
+    int win_l, int win_r, int bias_clip, float scale, int chunk, int lc,
     // Token-row strides in elements of q/k/v (reads) and dk/dv (writes).
     long sq, long sk, long sv, long sdk, long sdv) {
   constexpr int ROWB = H * 2;
@@ -541,13 +508,11 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
       stage_regular<H, QTB, NWB * WAVE_SIZE>(
           dout + (((long)b * T + qb) * N + n) * H, (long)N * H, T - qb,
           do_lds);
-      if (!(skip & 2)) {
-        stage_transposed<H, QTB, NWB * WAVE_SIZE, TP>(
-            q + ((long)b * T + qb) * sq + n * H, sq, T - qb, qt_lds);
-        stage_transposed<H, QTB, NWB * WAVE_SIZE, TP>(
-            dout + (((long)b * T + qb) * N + n) * H, (long)N * H, T - qb,
-            dot_lds);
-      }
+      stage_transposed<H, QTB, NWB * WAVE_SIZE, TP>(
+          q + ((long)b * T + qb) * sq + n * H, sq, T - qb, qt_lds);
+      stage_transposed<H, QTB, NWB * WAVE_SIZE, TP>(
+          dout + (((long)b * T + qb) * N + n) * H, (long)N * H, T - qb,
+          dot_lds);
       for (int i = threadIdx.x; i < QTB; i += NWB * WAVE_SIZE) {
         int qrow = qb + i;
         lse_s[i] = qrow < T ? lse[((long)b * N + n) * T + qrow] : NEG_INF;
@@ -668,7 +633,6 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
       }
 
       // Full dS tile to LDS (transposed store: ds_lds[q][key]) for dQ.
-      if (!(skip & 4))
 #pragma unroll
       for (int nf = 0; nf < NQ; ++nf) {
 #pragma unroll
@@ -685,7 +649,7 @@ __global__ __launch_bounds__(NWB * WAVE_SIZE) void fa_bwd_kernel(
       // dQ strips: rows q = qb + dw*16 + .. (A from ds_lds), B = K from
       // kt_lds; atomic-accumulate fp32. Only QTB/16 strips exist, so with
       // NWB > QTB/16 the extra waves skip this phase.
-      if (wid < QTB / 16 && !(skip & 1)) {
+      if (wid < QTB / 16) {
         f32x4 acc_dq[HF];
 #pragma unroll
         for (int hf = 0; hf < HF; ++hf) acc_dq[hf] = {0.f, 0.f, 0.f, 0.f};
@@ -815,12 +779,12 @@ __global__ void fa_dq_cast(const float* __restrict__ dq_acc,
 
 // ---------------------------------------------------------------------------
 // Backward, fused route: one workgroup per (head, batch), self-attention
-// with N == NKV and T == S <= NWF * SPW * 16.
+// with N == NKV and T == S <= FUSED_MAX_S.
 //
 // Keys across waves: strip s (16 keys) belongs to wave s % NWF, which keeps
 // the strip's K/V A-fragments and dK/dV accumulators in registers for the
 // whole kernel. The q-tiles are walked once. Per tile every wave writes its
-// dS strips into one [QTB][S_pad] LDS tile; after a barrier dQ^T = K^T dS^T
+// dS strips into one [FQTB][S_pad] LDS tile; after a barrier dQ^T = K^T dS^T
 // is computed over the whole key range (K^T resident in LDS), rounded once
 // and stored as bf16 straight into dq. delta = rowsum(dO * O) is reduced
 // while the dO tile is staged. Global loads for tile i+1 are issued into
@@ -828,25 +792,30 @@ __global__ void fa_dq_cast(const float* __restrict__ dq_acc,
 // summed in LDS by one owning thread each (fixed order, no atomics) and
 // leave as one fp32 row per workgroup for fa_dbias_reduce.
 // ---------------------------------------------------------------------------
-template <int NWF, int SPW>
-constexpr int fused_max_s() { return NWF * SPW * 16; }
+// 8 waves x 3 strips, 32-row q-tiles. Of the four configurations measured
+// (10x2 and 8x3 waves x strips, 64- and 32-row q-tiles) the only one that
+// keeps its accumulators out of scratch, and the fastest at the Conformer
+// shape (docs/KERNEL_NOTES.md).
+constexpr int FQTB = 32;                       // q rows per tile
+constexpr int NWF = 8;                         // waves
+constexpr int SPW = 3;                         // key strips per wave
+constexpr int FUSED_MAX_S = NWF * SPW * 16;
 
 // Dynamic LDS bytes of fa_bwd_fused_kernel (H == 64).
-template <int QTB, int NWF, int SPW>
 static size_t fused_lds_bytes(bool has_bias, bool bias_grad, int nbias) {
   constexpr int H = 64;
-  constexpr int SP = fused_max_s<NWF, SPW>();
-  return (size_t)QTB * H * 2 * 2           // q_lds + do_lds
+  constexpr int SP = FUSED_MAX_S;
+  return (size_t)FQTB * H * 2 * 2          // q_lds + do_lds
          + (size_t)H * 128 * 2             // qt_lds + dot_lds (128B pitch)
          + (size_t)H * SP * 2              // kt_lds
-         + (size_t)QTB * SP * 2            // ds_lds
+         + (size_t)FQTB * SP * 2           // ds_lds
          + (size_t)NWF * 16 * 128          // a_lds (128B pitch)
-         + 2 * QTB * sizeof(float)         // lse_s + delta_s
+         + 2 * FQTB * sizeof(float)        // lse_s + delta_s
          + (has_bias ? nbias * sizeof(float) : 0)
-         + (bias_grad ? (2 * SP + QTB) * sizeof(float) : 0);
+         + (bias_grad ? (2 * SP + FQTB) * sizeof(float) : 0);
 }
 
-template <int H, bool BIAS_GRAD, int QTB, int NWF, int SPW>
+template <int H, bool BIAS_GRAD>
 __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
     const unsigned short* __restrict__ dout,
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
@@ -860,19 +829,19 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
     long sq, long sk, long sv, long sdq, long sdk, long sdv) {
   static_assert(H == 64, "fused backward is built for H == 64");
   constexpr int NT = NWF * WAVE_SIZE;
-  constexpr int SP = fused_max_s<NWF, SPW>();  // padded key count
+  constexpr int SP = FUSED_MAX_S;  // padded key count
   constexpr int ROWB = H * 2;
   constexpr int KH = H / 32;
   constexpr int HF = H / 16;
-  constexpr int NQ = QTB / 16;
-  constexpr int TP = 128;        // pitch of the [..][QTB] tiles (swizzle span)
+  constexpr int NQ = FQTB / 16;
+  constexpr int TP = 128;        // pitch of the [..][FQTB] tiles (swizzle span)
   constexpr int DSP = SP * 2;    // pitch of the [..][SP] tiles
-  constexpr int NDACC = 2 * SP + QTB;
-  constexpr int STG = QTB * (ROWB / 16);       // staging threads (16B each)
+  constexpr int NDACC = 2 * SP + FQTB;
+  constexpr int STG = FQTB * (ROWB / 16);       // staging threads (16B each)
   static_assert(SP % 64 == 0, "[..][SP] rows must span whole swizzle blocks");
   static_assert((NWF * SPW) % 2 == 0, "dQ contracts over pairs of strips");
-  static_assert(QTB <= 64 && QTB % 16 == 0 && STG <= NT, "q-tile shape");
-  // dQ^T output tiles (QTB/16 x H/16) over the waves; a wave's tiles share
+  static_assert(FQTB <= 64 && FQTB % 16 == 0 && STG <= NT, "q-tile shape");
+  // dQ^T output tiles (FQTB/16 x H/16) over the waves; a wave's tiles share
   // their dS B-fragment.
   constexpr int NTILE = NQ * HF;
   constexpr int TPW = (NTILE + NWF - 1) / NWF;
@@ -880,16 +849,16 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
 
   const int nbias = 2 * bias_clip + 1;
   extern __shared__ char smem[];
-  char* q_lds = smem;                        // [QTB][H] swz
-  char* do_lds = q_lds + QTB * ROWB;         // [QTB][H] swz
-  char* qt_lds = do_lds + QTB * ROWB;        // [H][QTB] swz, pitch TP
-  char* dot_lds = qt_lds + H * TP;           // [H][QTB] swz, pitch TP
+  char* q_lds = smem;                        // [FQTB][H] swz
+  char* do_lds = q_lds + FQTB * ROWB;         // [FQTB][H] swz
+  char* qt_lds = do_lds + FQTB * ROWB;        // [H][FQTB] swz, pitch TP
+  char* dot_lds = qt_lds + H * TP;           // [H][FQTB] swz, pitch TP
   char* kt_lds = dot_lds + H * TP;           // [H][SP] swz
-  char* ds_lds = kt_lds + H * DSP;           // [QTB][SP] swz
-  char* a_lds = ds_lds + QTB * DSP;          // [NWF][16][QTB] swz, pitch TP
-  float* lse_s = (float*)(a_lds + NWF * 16 * TP);       // [QTB]
-  float* delta_s = lse_s + QTB;                         // [QTB]
-  float* bias_s = delta_s + QTB;                        // [nbias] if bias
+  char* ds_lds = kt_lds + H * DSP;           // [FQTB][SP] swz
+  char* a_lds = ds_lds + FQTB * DSP;          // [NWF][16][FQTB] swz, pitch TP
+  float* lse_s = (float*)(a_lds + NWF * 16 * TP);       // [FQTB]
+  float* delta_s = lse_s + FQTB;                         // [FQTB]
+  float* bias_s = delta_s + FQTB;                        // [nbias] if bias
   // Unclipped per-diagonal sums, slot = (q - key) + SP - 1.
   float* dacc = bias_s + (bias ? nbias : 0);            // [NDACC] if BIAS_GRAD
 
@@ -904,18 +873,18 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
   const int klen = klen_ptr ? min(max(klen_ptr[b], 0), S) : S;
   const int nact = (klen + 15) / 16;          // strips with a visible key
   const int kact = ((nact + 1) & ~1) * 16;    // dQ contraction length
-  const int nqt = (T + QTB - 1) / QTB;
+  const int nqt = (T + FQTB - 1) / FQTB;
   // Window half-widths with "no limit" folded in (T <= SP keeps the sums
   // far from overflow).
   const int wl = win_l < 0 ? 0x3fffffff : win_l;
   const int wr = win_r < 0 ? 0x3fffffff : win_r;
 
-  // Staging role of this thread: 16 bytes of one q/dO/O row; the last QTB
+  // Staging role of this thread: 16 bytes of one q/dO/O row; the last FQTB
   // threads carry lse.
   const int srow = tid / (ROWB / 16);
   const int sc = tid % (ROWB / 16);
   const bool stager = tid < STG;
-  const int lrow = tid - (NT - QTB);
+  const int lrow = tid - (NT - FQTB);
   ushortx8 pq, pdo, po;
   float plse = 0.f;
 #pragma unroll
@@ -938,7 +907,7 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
 
   // One-time LDS setup: dS tile zeroed (columns of the odd padding strip
   // are read by dQ but never written), bias row, diagonal sums, K^T.
-  for (int i = tid; i < QTB * DSP / 16; i += NT) {
+  for (int i = tid; i < FQTB * DSP / 16; i += NT) {
     ushortx8 z;
 #pragma unroll
     for (int j = 0; j < 8; ++j) z[j] = 0;
@@ -993,7 +962,7 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
 
   char* aw = a_lds + wid * 16 * TP;
   for (int qt = 0; qt < nqt; ++qt) {
-    const int qb = qt * QTB;
+    const int qb = qt * FQTB;
     // No barrier here: q/dO/lse/delta were last read before the barrier
     // that ends the strip phase, and the dS tile and dacc are next written
     // after the barrier below.
@@ -1026,14 +995,14 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
     }
     if (lrow >= 0) lse_s[lrow] = qb + lrow < T ? plse : NEG_INF;
     __syncthreads();
-    if (qt + 1 < nqt) prefetch(qb + QTB);
+    if (qt + 1 < nqt) prefetch(qb + FQTB);
 
 #pragma unroll
     for (int si = 0; si < SPW; ++si) {
       const int strip = wid + si * NWF;
       if (strip >= nact) continue;   // wave-uniform
       const int k0 = strip * 16;
-      // S^T strip: rows = 16 keys, cols = QTB queries.
+      // S^T strip: rows = 16 keys, cols = FQTB queries.
       float pt[NQ][4];   // P^T
       float dlg[NQ][4];  // dLogits
 #pragma unroll
@@ -1078,7 +1047,7 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
         }
       }
 #pragma unroll
-      for (int kk2 = 0; kk2 < QTB / 32; ++kk2) {
+      for (int kk2 = 0; kk2 < FQTB / 32; ++kk2) {
         bf16x8 pa = lds_frag(aw, cl, TP, (kk2 * 32 + g * 8) * 2);
 #pragma unroll
         for (int hf = 0; hf < HF; ++hf) {
@@ -1122,7 +1091,7 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
       }
       // dK += dS^T @ Q (B = Qt).
 #pragma unroll
-      for (int kk2 = 0; kk2 < QTB / 32; ++kk2) {
+      for (int kk2 = 0; kk2 < FQTB / 32; ++kk2) {
         bf16x8 da = lds_frag(aw, cl, TP, (kk2 * 32 + g * 8) * 2);
 #pragma unroll
         for (int hf = 0; hf < HF; ++hf) {
@@ -1169,11 +1138,11 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
       // dlogits*scale; invisible positions are exact zeros), handed out
       // from the last thread down so the waves without a dQ tile go first.
       // A slot of dacc has one owner per tile: plain read-modify-write.
-      const int ndiag = QTB + kact - 1;
+      const int ndiag = FQTB + kact - 1;
       for (int di = NT - 1 - tid; di < ndiag; di += NT) {
         const int doff = di - (kact - 1);   // qrow - key within the tile
         const int q_lo = max(0, doff);
-        const int q_hi = min(QTB - 1, kact - 1 + doff);
+        const int q_hi = min(FQTB - 1, kact - 1 + doff);
         float sum = 0.f;
         for (int qrow = q_lo; qrow <= q_hi; ++qrow) {
           const int key = qrow - doff;
@@ -1260,6 +1229,74 @@ static size_t fa_lds_limit_bytes() {
   return (size_t)limit;
 }
 
+// One launch function per kernel, and a dispatch from the run-time values to
+// its template arguments; the kernel arguments pass through.
+template <int H, int KTF, bool SEG, class... Args>
+static void fa_fwd_launch(dim3 grid, hipStream_t stream, Args... args) {
+  const size_t shmem =
+      (size_t)KTF * H * 2 + (size_t)H * KTF * 2 + FWD_NW * 16 * KTF * 2;
+  hipLaunchKernelGGL((fa_fwd_kernel<H, KTF, SEG>), grid, dim3(FWD_BLOCK),
+                     shmem, stream, args...);
+}
+
+template <int H, int KTF, class... Args>
+static void fa_fwd_dispatch_seg(bool seg, Args... args) {
+  if (seg) {
+    fa_fwd_launch<H, KTF, true>(args...);
+  } else {
+    fa_fwd_launch<H, KTF, false>(args...);
+  }
+}
+
+template <class... Args>
+static void fa_fwd_dispatch(int H, int ktf, bool seg, Args... args) {
+  if (H == 64 && ktf == 128) {
+    fa_fwd_dispatch_seg<64, 128>(seg, args...);
+  } else if (H == 64) {
+    fa_fwd_dispatch_seg<64, 64>(seg, args...);
+  } else if (ktf == 128) {
+    fa_fwd_dispatch_seg<128, 128>(seg, args...);
+  } else {
+    fa_fwd_dispatch_seg<128, 64>(seg, args...);
+  }
+}
+
+template <int H, bool BIAS_GRAD, class... Args>
+static void fa_bwd_launch(dim3 grid, size_t shmem, hipStream_t stream,
+                          Args... args) {
+  hipLaunchKernelGGL((fa_bwd_kernel<H, BIAS_GRAD>), grid,
+                     dim3(NWB * WAVE_SIZE), shmem, stream, args...);
+}
+
+template <class... Args>
+static void fa_bwd_dispatch(int H, bool bias_grad, Args... args) {
+  if (H == 64 && bias_grad) {
+    fa_bwd_launch<64, true>(args...);
+  } else if (H == 64) {
+    fa_bwd_launch<64, false>(args...);
+  } else if (bias_grad) {
+    fa_bwd_launch<128, true>(args...);
+  } else {
+    fa_bwd_launch<128, false>(args...);
+  }
+}
+
+template <bool BIAS_GRAD, class... Args>
+static void fa_bwd_fused_launch(dim3 grid, size_t shmem, hipStream_t stream,
+                                Args... args) {
+  hipLaunchKernelGGL((fa_bwd_fused_kernel<64, BIAS_GRAD>), grid,
+                     dim3(NWF * WAVE_SIZE), shmem, stream, args...);
+}
+
+template <class... Args>
+static void fa_bwd_fused_dispatch(bool bias_grad, Args... args) {
+  if (bias_grad) {
+    fa_bwd_fused_launch<true>(args...);
+  } else {
+    fa_bwd_fused_launch<false>(args...);
+  }
+}
+
 static void check_btnh(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 4 &&
                   t.scalar_type() == torch::kBFloat16,
@@ -1321,63 +1358,13 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
   // Big KV tiles amortize staging barriers, but waste work on short
   // sequences (masked overhang): pick by S.
   const int ktf = S >= 512 ? 128 : 64;
-  size_t shmem =
-      (size_t)ktf * H * 2 + (size_t)H * ktf * 2 + FWD_NW * 16 * ktf * 2;
-#define FA_FWD(HH)                                                          \
-  if (ktf == 128)                                                           \
-    hipLaunchKernelGGL((fa_fwd_kernel<HH, 128, false>), grid,               \
-                       dim3(FWD_BLOCK),                                     \
-                       shmem, stream,                                       \
-                     (const unsigned short*)q.data_ptr(),                   \
-                     (const unsigned short*)k.data_ptr(),                   \
-                     (const unsigned short*)v.data_ptr(), klp, bp, qsp,     \
-                     ksp, (unsigned short*)o.data_ptr(),                    \
-                     lse.data_ptr<float>(), B, T, S, N, NKV, (int)win_l,    \
-                     (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv)
-#define FA_FWD64(HH)                                                        \
-  hipLaunchKernelGGL((fa_fwd_kernel<HH, 64, false>), grid,                  \
-                     dim3(FWD_BLOCK),                                       \
-                     shmem, stream, (const unsigned short*)q.data_ptr(),    \
-                     (const unsigned short*)k.data_ptr(),                   \
-                     (const unsigned short*)v.data_ptr(), klp, bp, qsp,     \
-                     ksp, (unsigned short*)o.data_ptr(),                    \
-                     lse.data_ptr<float>(), B, T, S, N, NKV, (int)win_l,    \
-                     (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv)
-#define FA_FWD_SEG(HH)                                                      \
-  if (ktf == 128)                                                           \
-    hipLaunchKernelGGL((fa_fwd_kernel<HH, 128, true>), grid,                \
-                       dim3(FWD_BLOCK), shmem, stream,                      \
-                       (const unsigned short*)q.data_ptr(),                 \
-                       (const unsigned short*)k.data_ptr(),                 \
-                       (const unsigned short*)v.data_ptr(), klp, bp, qsp,   \
-                       ksp, (unsigned short*)o.data_ptr(),                  \
-                       lse.data_ptr<float>(), B, T, S, N, NKV, (int)win_l,  \
-                       (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv);           \
-  else                                                                      \
-    hipLaunchKernelGGL((fa_fwd_kernel<HH, 64, true>), grid,                 \
-                       dim3(FWD_BLOCK), shmem, stream,                      \
-                       (const unsigned short*)q.data_ptr(),                 \
-                       (const unsigned short*)k.data_ptr(),                 \
-                       (const unsigned short*)v.data_ptr(), klp, bp, qsp,   \
-                       ksp, (unsigned short*)o.data_ptr(),                  \
-                       lse.data_ptr<float>(), B, T, S, N, NKV, (int)win_l,  \
-                       (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv)
-  if (qsp != nullptr) {
-    if (H == 64) {
-      FA_FWD_SEG(64);
-    } else {
-      FA_FWD_SEG(128);
-    }
-  } else if (H == 64) {
-    FA_FWD(64);
-    else FA_FWD64(64);
-  } else {
-    FA_FWD(128);
-    else FA_FWD64(128);
-  }
-#undef FA_FWD
-#undef FA_FWD64
-#undef FA_FWD_SEG
+  fa_fwd_dispatch(H, ktf, qsp != nullptr, grid, stream.stream(),
+                  (const unsigned short*)q.data_ptr(),
+                  (const unsigned short*)k.data_ptr(),
+                  (const unsigned short*)v.data_ptr(), klp, bp, qsp, ksp,
+                  (unsigned short*)o.data_ptr(), lse.data_ptr<float>(), B, T,
+                  S, N, NKV, (int)win_l, (int)win_r, (int)bias_clip,
+                  (float)scale, (int)chunk_size, (int)left_chunks, sq, sk, sv);
   return {o, lse};
 }
 
@@ -1439,42 +1426,18 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
        bias->numel() == (long)N * nbias);
 
   // Route, from shapes only (no device read, so the step still captures
-  // into a graph). 'fused' is the default fused configuration; the
-  // 'fused_*' names pick one configuration for A/B measurements.
-  enum { kTiles, kF10x2q64, kF8x3q64, kF10x2q32, kF8x3q32 } cfg = kTiles;
-  const bool want_fused = route.rfind("fused", 0) == 0;
-  TORCH_CHECK(route == "auto" || route == "tiles" || route == "fused" ||
-                  route == "fused_10x2_q64" || route == "fused_8x3_q64" ||
-                  route == "fused_10x2_q32" || route == "fused_8x3_q32",
+  // into a graph).
+  bool fused = false;
+  TORCH_CHECK(route == "auto" || route == "tiles" || route == "fused",
               "fa_bwd: unknown route '", route, "'");
-  size_t fused_lds = 0;
+  const size_t fused_lds = fused_lds_bytes(bias.has_value(), bg, nbias);
   if (route != "tiles") {
-    int max_s;
-    if (route == "fused_8x3_q64") {
-      cfg = kF8x3q64;
-      max_s = fused_max_s<8, 3>();
-      fused_lds = fused_lds_bytes<64, 8, 3>(bias.has_value(), bg, nbias);
-    } else if (route == "fused_10x2_q64") {
-      cfg = kF10x2q64;
-      max_s = fused_max_s<10, 2>();
-      fused_lds = fused_lds_bytes<64, 10, 2>(bias.has_value(), bg, nbias);
-    } else if (route == "fused_10x2_q32") {
-      cfg = kF10x2q32;
-      max_s = fused_max_s<10, 2>();
-      fused_lds = fused_lds_bytes<32, 10, 2>(bias.has_value(), bg, nbias);
-    } else {
-      // Default: 8 waves x 3 strips, 32-row q-tiles. The only one of the
-      // four that keeps its accumulators out of scratch, and the fastest
-      // at the Conformer shape (docs/KERNEL_NOTES.md).
-      cfg = kF8x3q32;
-      max_s = fused_max_s<8, 3>();
-      fused_lds = fused_lds_bytes<32, 8, 3>(bias.has_value(), bg, nbias);
-    }
+    fused = true;
     const char* why = nullptr;
     if (H != 64) why = "H != 64";
     else if (group != 1) why = "N != NKV";
     else if (T != S) why = "T != S";
-    else if (S > max_s) why = "S above the route's limit";
+    else if (S > FUSED_MAX_S) why = "S above the route's limit";
     else if (qseg.has_value() || kseg.has_value()) why = "segment ids";
     else if (chunk_size > 0) why = "chunkwise mask";
     else if (B > 65535) why = "B above the grid limit";
@@ -1485,9 +1448,9 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
       why = "lse is not fp32 [B,N,T]";
     else if (fused_lds > fa_lds_limit_bytes()) why = "LDS request too large";
     if (why) {
-      TORCH_CHECK(!want_fused, "fa_bwd: route '", route,
+      TORCH_CHECK(route != "fused", "fa_bwd: route '", route,
                   "' does not support this call: ", why);
-      cfg = kTiles;
+      fused = false;
     }
   }
 
@@ -1496,7 +1459,7 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
   const unsigned short* bp =
       bias.has_value() ? (const unsigned short*)bias->data_ptr() : nullptr;
 
-  if (cfg != kTiles) {
+  if (fused) {
     torch::Tensor dq_t, dk_t, dv_t;
     if (into) {
       dq_t = *dq_out;
@@ -1516,30 +1479,17 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
                            bias.has_value() ? nbias : 0}, fopts);
     torch::Tensor part;
     if (bg) part = torch::empty({B, N, nbias}, fopts);
-    dim3 grid(N, B);
-#define FA_BWD_FUSED(BG, QTB, NWF, SPW)                                      \
-  hipLaunchKernelGGL(                                                        \
-      (fa_bwd_fused_kernel<64, BG, QTB, NWF, SPW>), grid,                    \
-      dim3(NWF * WAVE_SIZE), fused_lds, stream,                              \
-      (const unsigned short*)dout.data_ptr(),                                \
-      (const unsigned short*)q.data_ptr(),                                   \
-      (const unsigned short*)k.data_ptr(),                                   \
-      (const unsigned short*)v.data_ptr(),                                   \
-      (const unsigned short*)o.data_ptr(), lse.data_ptr<float>(), klp, bp,   \
-      (unsigned short*)dq_t.data_ptr(), (unsigned short*)dk_t.data_ptr(),    \
-      (unsigned short*)dv_t.data_ptr(),                                      \
-      bg ? part.data_ptr<float>() : nullptr, T, N, (int)win_l, (int)win_r,   \
-      (int)bias_clip, (float)scale, sq, sk, sv, sdq, sdk, sdv)
-    if (cfg == kF10x2q64) {
-      if (bg) FA_BWD_FUSED(true, 64, 10, 2); else FA_BWD_FUSED(false, 64, 10, 2);
-    } else if (cfg == kF8x3q64) {
-      if (bg) FA_BWD_FUSED(true, 64, 8, 3); else FA_BWD_FUSED(false, 64, 8, 3);
-    } else if (cfg == kF8x3q32) {
-      if (bg) FA_BWD_FUSED(true, 32, 8, 3); else FA_BWD_FUSED(false, 32, 8, 3);
-    } else {
-      if (bg) FA_BWD_FUSED(true, 32, 10, 2); else FA_BWD_FUSED(false, 32, 10, 2);
-    }
-#undef FA_BWD_FUSED
+    fa_bwd_fused_dispatch(
+        bg, dim3(N, B), fused_lds, stream.stream(),
+        (const unsigned short*)dout.data_ptr(),
+        (const unsigned short*)q.data_ptr(),
+        (const unsigned short*)k.data_ptr(),
+        (const unsigned short*)v.data_ptr(),
+        (const unsigned short*)o.data_ptr(), lse.data_ptr<float>(), klp, bp,
+        (unsigned short*)dq_t.data_ptr(), (unsigned short*)dk_t.data_ptr(),
+        (unsigned short*)dv_t.data_ptr(),
+        bg ? part.data_ptr<float>() : nullptr, T, N, (int)win_l, (int)win_r,
+        (int)bias_clip, (float)scale, sq, sk, sv, sdq, sdk, sdv);
     if (bg) {
       const int D = N * nbias;
       hipLaunchKernelGGL(fa_dbias_reduce, dim3(cdiv(D, WAVE_SIZE)),
@@ -1552,19 +1502,13 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
 
   auto delta = torch::empty({B, N, T}, q.options().dtype(torch::kFloat32));
   {
-    long rows = (long)B * T * N;
-    const int rpb = BLOCK / (H / 8);  // rows per block, H/8 lanes per row
-    dim3 grid((rows + rpb - 1) / rpb);
-    if (H == 64)
-      hipLaunchKernelGGL((fa_bwd_delta<64>), grid, dim3(BLOCK), 0, stream,
-                         (const unsigned short*)dout.data_ptr(),
-                         (const unsigned short*)o.data_ptr(),
-                         delta.data_ptr<float>(), B, T, N);
-    else
-      hipLaunchKernelGGL((fa_bwd_delta<128>), grid, dim3(BLOCK), 0, stream,
-                         (const unsigned short*)dout.data_ptr(),
-                         (const unsigned short*)o.data_ptr(),
-                         delta.data_ptr<float>(), B, T, N);
+    const long rows = (long)B * T * N;
+    auto kernel = H == 64 ? attn_delta_kernel<64> : attn_delta_kernel<128>;
+    hipLaunchKernelGGL(kernel, dim3(cdiv(rows, DELTA_BLOCK / (H / 8))),
+                       dim3(DELTA_BLOCK), 0, stream,
+                       (const unsigned short*)dout.data_ptr(),
+                       (const unsigned short*)o.data_ptr(),
+                       delta.data_ptr<float>(), B, T, N);
   }
 
   auto fopts = q.options().dtype(torch::kFloat32);
@@ -1587,47 +1531,17 @@ std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
   const int* qsp = qseg.has_value() ? qseg->data_ptr<int>() : nullptr;
   const int* ksp = kseg.has_value() ? kseg->data_ptr<int>() : nullptr;
 
-  // Phase-skip bitmask for perf attribution only (results invalid when
-  // nonzero): 1 = skip dQ math+atomics, 2 = skip transposed q/do
-  // staging, 4 = skip dS-full store.
-  static int skip_phases = []() {
-    const char* e = getenv("LINGVO_FA_BWD_SKIP");
-    return e ? atoi(e) : 0;
-  }();
-  // 128-key tiles with 8 waves (q-tile staging amortized 2x). H=128
-  // uses 144KB LDS -> 1 block/CU; staging savings outweigh occupancy.
-  const int ktb = 128;
-  const int nwb = 8;
-  // q-tile 64. A 32-row variant (2 blocks/CU via ~64 KB LDS) measured
-  // SLOWER (bwd 0.73 -> 0.81 ms at the bench shape): doubled staging
-  // sync passes outweigh the occupancy gain. QTB stays a template knob.
-  const int qtb = 64;
-  size_t shmem = (size_t)qtb * H * 2 * 2     // q_lds + do_lds
-                 + (size_t)H * 128 * 2       // qt_lds + dot_lds (128B pitch)
-                 + (size_t)H * ktb * 2       // kt_lds
-                 + (size_t)qtb * ktb * 2     // ds_lds
-                 + (size_t)nwb * 16 * 128    // a_lds (128B pitch)
-                 + 2 * qtb * sizeof(float) + (bg ? nbias * sizeof(float) : 0);
-  dim3 grid((S + ktb - 1) / ktb, NKV, B);
-#define FA_BWD(HH, BG)                                                       \
-  hipLaunchKernelGGL(                                                        \
-      (fa_bwd_kernel<HH, BG, 128, 8, 64>), grid, dim3(8 * WAVE_SIZE), shmem, \
-      stream,                                                                \
-      (const unsigned short*)dout.data_ptr(),                                \
-      (const unsigned short*)q.data_ptr(),                                   \
-      (const unsigned short*)k.data_ptr(),                                   \
-      (const unsigned short*)v.data_ptr(), lse.data_ptr<float>(),            \
-      delta.data_ptr<float>(), klp, bp, qsp, ksp,                            \
-      dq_acc.data_ptr<float>(),                                              \
-      (unsigned short*)dk_t.data_ptr(), (unsigned short*)dv_t.data_ptr(),    \
-      dbias_t.numel() ? dbias_t.data_ptr<float>() : nullptr, B, T, S, N,     \
-      NKV, (int)win_l, (int)win_r, (int)bias_clip, (float)scale, skip_phases, (int)chunk_size, (int)left_chunks, sq, sk, sv, sdk, sdv)
-  if (H == 64) {
-    if (bg) FA_BWD(64, true); else FA_BWD(64, false);
-  } else {
-    if (bg) FA_BWD(128, true); else FA_BWD(128, false);
-  }
-#undef FA_BWD
+  fa_bwd_dispatch(
+      H, bg, dim3((S + KTB - 1) / KTB, NKV, B), bwd_lds_bytes(H, bg, nbias),
+      stream.stream(), (const unsigned short*)dout.data_ptr(),
+      (const unsigned short*)q.data_ptr(),
+      (const unsigned short*)k.data_ptr(),
+      (const unsigned short*)v.data_ptr(), lse.data_ptr<float>(),
+      delta.data_ptr<float>(), klp, bp, qsp, ksp, dq_acc.data_ptr<float>(),
+      (unsigned short*)dk_t.data_ptr(), (unsigned short*)dv_t.data_ptr(),
+      dbias_t.numel() ? dbias_t.data_ptr<float>() : nullptr, B, T, S, N, NKV,
+      (int)win_l, (int)win_r, (int)bias_clip, (float)scale, (int)chunk_size,
+      (int)left_chunks, sq, sk, sv, sdk, sdv);
 
   torch::Tensor dq;
   if (into) {

@@ -36,11 +36,14 @@
 #include "host_checks.h"
 #include "mfma.h"
 
-// Device code of this file is built without the packed-fp32 VALU forms.
+// Device code of this file is built without the packed-fp32 VALU forms; the
+// tile helpers are included inside the region so that theirs is too.
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute push(                                      \
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
+
+#include "attn_tile.h"
 
 namespace {
 
@@ -52,24 +55,6 @@ constexpr int XBLOCK = XNW * WAVE_SIZE;
 constexpr int XWIN = 128;           // staged window rows (127 used)
 constexpr int ROWB = XH * 2;        // bytes of a 64-element bf16 row
 constexpr int WINB = XWIN * 2;      // pitch of a [.][window] tile
-constexpr float NEG_INF = -1e30f;
-
-__device__ __forceinline__ bf16x8 lds_frag(const char* tile, int row,
-                                           int rowb, int byte_in_row) {
-  union {
-    ushortx8 u;
-    bf16x8 h;
-  } cv;
-  cv.u = *reinterpret_cast<const ushortx8*>(tile + row * rowb +
-                                            swz(row, byte_in_row));
-  return cv.h;
-}
-
-__device__ __forceinline__ void lds_put(char* tile, int row, int rowb,
-                                        int col, unsigned short bits) {
-  *reinterpret_cast<unsigned short*>(tile + row * rowb + swz(row, col * 2)) =
-      bits;
-}
 
 // 8 elements of row `row` (rows >= valid are zeros), plus add[0..8) if given:
 // the fp32 add first, then one rounding to bf16.
@@ -355,29 +340,6 @@ __global__ __launch_bounds__(XBLOCK) void xl_fwd_kernel(
 // ---------------------------------------------------------------------------
 // Backward
 // ---------------------------------------------------------------------------
-// delta[b,n,t] = sum_h dO * O; 8 neighbouring lanes per (b,t,n) row.
-__global__ __launch_bounds__(XBLOCK) void xl_delta_kernel(
-    const unsigned short* __restrict__ dout,
-    const unsigned short* __restrict__ o, float* __restrict__ delta, long nrows,
-    int T, int N) {
-  const long row = (long)blockIdx.x * (XBLOCK / 8) + threadIdx.x / 8;
-  const int c = threadIdx.x & 7;
-  const long lrow = row < nrows ? row : nrows - 1;  // whole waves shuffle
-  const ushortx8 d8 =
-      *reinterpret_cast<const ushortx8*>(dout + lrow * XH + c * 8);
-  const ushortx8 o8 = *reinterpret_cast<const ushortx8*>(o + lrow * XH + c * 8);
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    sum += bf16_bits_to_float(d8[j]) * bf16_bits_to_float(o8[j]);
-#pragma unroll
-  for (int off = 1; off < 8; off <<= 1) sum += __shfl_xor(sum, off);
-  if (c == 0 && row < nrows) {
-    const long bb = row / ((long)T * N), tn = row % ((long)T * N);
-    delta[(bb * N + tn % N) * T + tn / N] = sum;
-  }
-}
-
 constexpr size_t kBwdLds =
     3 * XK * ROWB              // k_lds, kt_lds, v_lds
     + 2 * XWIN * ROWB          // win, wint
@@ -737,9 +699,10 @@ std::vector<torch::Tensor> xl_attn_bwd(torch::Tensor dout, torch::Tensor q,
   const int D = s.N * XH;
 
   auto delta = torch::empty({s.B, s.N, s.T}, fopts);
-  hipLaunchKernelGGL(xl_delta_kernel, dim3(cdiv(rows * s.N, XBLOCK / 8)),
-                     dim3(XBLOCK), 0, stream, u16(dout), u16(o),
-                     delta.data_ptr<float>(), rows * s.N, s.T, s.N);
+  hipLaunchKernelGGL(attn_delta_kernel<XH>,
+                     dim3(cdiv(rows * s.N, DELTA_BLOCK / (XH / 8))),
+                     dim3(DELTA_BLOCK), 0, stream, u16(dout), u16(o),
+                     delta.data_ptr<float>(), s.B, s.T, s.N);
 
   auto dqc = torch::zeros({s.B, s.T, s.N, XH}, fopts);
   auto dqp = torch::zeros({s.B, s.T, s.N, XH}, fopts);

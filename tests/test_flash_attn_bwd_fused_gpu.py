@@ -20,7 +20,7 @@ gpu = pytest.mark.gpu
 
 H = 64
 # Largest S the default fused configuration takes (8 waves x 3 strips of
-# 16 keys); flash_attn.hip fused_max_s.
+# 16 keys); flash_attn.hip FUSED_MAX_S.
 MAX_S = 384
 
 CASES = {
@@ -168,8 +168,9 @@ def test_above_the_limit_takes_tiles():
       float(tiles[0].float().abs().max()))
   with pytest.raises(RuntimeError, match='does not support'):
     _Bwd(x, o, lse, 'fused')
-  with pytest.raises(RuntimeError, match='unknown route'):
-    _Bwd(x, o, lse, 'fastest')
+  for name in ('fastest', 'fused_8x3_q32'):
+    with pytest.raises(RuntimeError, match='unknown route'):
+      _Bwd(x, o, lse, name)
 
 
 @gpu

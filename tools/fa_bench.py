@@ -1,7 +1,7 @@
 """Flash-attention microbenchmark at Conformer-L bench shapes.
 
   python tools/fa_bench.py [--shape conformer|lm] [--iters 50]
-                           [--batch B] [--route auto|tiles|fused|...]
+                           [--batch B] [--route auto|tiles|fused]
                            [--ab [--rounds 5] [--ab-iters 3]]
 
 Times fwd and bwd separately (bwd via retained graph + backward on a
@@ -10,7 +10,7 @@ fixed grad), prints achieved TFLOP/s against the attention flop count
 
 --ab times the backward routes interleaved round by round in one process
 (each figure includes everything the route launches: fill, delta and cast
-for 'tiles', the dbias reduce for the fused ones) and prints per-route
+for 'tiles', the dbias reduce for 'fused') and prints per-route
 median and min over the rounds.
 """
 
@@ -48,8 +48,7 @@ def main():
   ap.add_argument('--batch', type=int, default=0,
                   help='override the shape\'s batch size')
   ap.add_argument('--route', default='auto',
-                  help='fa_bwd route: auto, tiles, fused or a fused_* '
-                  'configuration')
+                  help='fa_bwd route: auto, tiles or fused')
   ap.add_argument('--ab', action='store_true',
                   help='interleaved A/B of the backward routes')
   ap.add_argument('--rounds', type=int, default=5)
@@ -98,8 +97,7 @@ def main():
   print(f'shape={args.shape} B={B} T={T} N={N} H={H} '
         f'bias={"clip" + str(clip) if bias is not None else "none"}')
   if args.ab:
-    routes = ['tiles', 'fused_10x2_q64', 'fused_8x3_q64', 'fused_10x2_q32',
-              'fused_8x3_q32']
+    routes = ['tiles', 'fused']
     times = {r: [] for r in routes}
     for r in routes:  # warm up every route
       bwd(r)
