@@ -8,11 +8,13 @@ attention_util.py:656 KMeansClusteringForAtten; favor_attention.py
 FAVOR+). All share MultiHeadedAttention's projections and FProp
 surface, so they are drop-in `atten_tpl` choices.
 
-These variants reshape the problem rather than the kernel: chunkwise
-runs the dense flash kernel per chunk; routing gathers per-cluster key
-subsets then runs dense attention; Performer replaces softmax with a
-random-feature kernel so attention is two GEMMs (prefix sums when
-causal) — all GEMM-shaped work lands on MFMA via hipBLASLt.
+Chunkwise runs its mask inside the flash kernel; routing reshapes the
+problem rather than the kernel (it gathers per-cluster key subsets, then
+runs dense attention). Performer replaces softmax with a random-feature
+kernel and has kernels of its own: bf16 CUDA tensors run the chunked
+linear-attention scan of ops/favor_attn.py, with the feature map fused in
+and no [B,T,N,m] or [B,T,N,m,H] tensor; elsewhere it is composed torch, two
+GEMMs (prefix sums when causal).
 """
 
 from __future__ import annotations
@@ -26,6 +28,7 @@ import torch.nn.functional as F
 from lingvo_amd.core import py_utils
 from lingvo_amd.core.nested_map import NestedMap
 from lingvo_amd.layers import attention as attention_lib
+from lingvo_amd.ops import favor_attn
 from lingvo_amd.ops import flash_attn
 
 
@@ -164,18 +167,32 @@ class PerformerAttention(attention_lib.MultiHeadedAttention):
   """FAVOR+ linear attention (reference favor_attention.py; Choromanski
   et al. 2021). Positive random features phi(x) = exp(w.x - |x|^2/2)
   give an unbiased softmax estimate; attention becomes two GEMMs
-  (prefix sums when causal): O(T * m * H)."""
+  (prefix sums when causal): O(T * m * H).
+
+  Two routes, chosen by `favor_impl` and the projected tensors: bf16 CUDA
+  tensors with dim_per_head 64 and a feature count that is a multiple of 32
+  up to 128 run, under favor_impl='auto', the gfx950 kernels of
+  ops/favor_attn.py (a chunked scan that keeps the [m, H] state in registers;
+  no per-position feature or outer-product tensor exists forward or
+  backward). Everything else - CPU, other head dims, feature counts or
+  dtypes, favor_impl='torch' - runs the composed einsum form, whose causal
+  branch materializes [B, T, N, m, H] prefix sums."""
 
   @classmethod
   def Params(cls):
     p = super().Params()
     p.Define('num_random_features', 128, 'Feature count m.')
     p.Define('redraw_each_step', False, 'Resample features every FProp.')
+    p.Define('favor_impl', 'auto',
+             "Attention-core route: 'auto' (HIP kernels on bf16 CUDA with "
+             "dim_per_head 64 and num_random_features % 32 == 0, <= 128, "
+             "composed torch elsewhere) or 'torch' (always composed).")
     p.cls = cls
     return p
 
   def __init__(self, params):
     super().__init__(params)
+    assert self.p.favor_impl in ('auto', 'torch'), self.p.favor_impl
     g = torch.Generator().manual_seed(
         (self.p.random_seed or 1234) & 0x7FFFFFFF)
     self.register_buffer('proj_mat', self._Orthogonal(g))
@@ -195,8 +212,9 @@ class PerformerAttention(attention_lib.MultiHeadedAttention):
     # stabilizer must be CONSTANT across key positions (else it
     # reweights the softmax), so keys share one per-(B,N) max; a
     # per-query stabilizer cancels in the num/den ratio and is fine.
-    xs = x.float() * math.sqrt(scale)
-    wx = torch.einsum('btnh,mh->btnm', xs, self.proj_mat.float())
+    ft = torch.float64 if x.dtype == torch.float64 else torch.float32
+    xs = x.to(ft) * math.sqrt(scale)
+    wx = torch.einsum('btnh,mh->btnm', xs, self.proj_mat.to(ft))
     z = wx - 0.5 * (xs * xs).sum(-1, keepdim=True)
     if is_key:
       stab = z.amax(dim=(1, 3), keepdim=True).detach()
@@ -218,12 +236,35 @@ class PerformerAttention(attention_lib.MultiHeadedAttention):
     n, h = self._n, self._h
     assert self._nkv == n, 'Performer requires full KV heads'
     q, k, v = self._Project(theta, query_vec)
-    scale = 1.0 / math.sqrt(h)
+    if (p.favor_impl == 'auto' and q.is_cuda and q.dtype == torch.bfloat16
+        and favor_attn.kernel_supports(h, p.num_random_features)):
+      ctx = self._KernelContext(q, k, v, paddings)
+    else:
+      ctx = self._ComposedContext(q, k, v, paddings)
+    ctx = ctx.reshape(b, t, n * h).to(query_vec.dtype)
+    post = py_utils.MatmulBias(ctx, theta.post_w,
+                               theta.post_b if p.use_bias else None)
+    if paddings is not None:
+      post = py_utils.ApplyPadding(paddings, post)
+    return post
+
+  def _KernelContext(self, q, k, v, paddings):
+    """[B,T,N,H] context vectors from ops/favor_attn.py."""
+    klen = (py_utils.LengthsFromPaddings(paddings).to(torch.int32)
+            if paddings is not None else None)
+    return favor_attn.favor_attention(q, k, v, self.proj_mat, klen=klen,
+                                      causal=self.p.causal)
+
+  def _ComposedContext(self, q, k, v, paddings):
+    """[B,T,N,H] context vectors from composed einsums in fp32 (fp64 for
+    fp64 inputs)."""
+    p = self.p
+    scale = 1.0 / math.sqrt(self._h)
     qp = self._Phi(q, scale, is_key=False)   # [B,T,N,m]
     kp = self._Phi(k, scale, is_key=True)
     if paddings is not None:
       kp = kp * (1.0 - paddings)[:, :, None, None]
-    vf = v.float()
+    vf = v.to(qp.dtype)
     if p.causal:
       # prefix sums over time
       kv = torch.einsum('btnm,btnh->btnmh', kp, vf).cumsum(1)
@@ -235,13 +276,7 @@ class PerformerAttention(attention_lib.MultiHeadedAttention):
       z = kp.sum(1)  # [B,N,m]
       num = torch.einsum('btnm,bnmh->btnh', qp, kv)
       den = torch.einsum('btnm,bnm->btn', qp, z).clamp_min(1e-6)
-    ctx = (num / den.unsqueeze(-1)).reshape(b, t, n * h).to(
-        query_vec.dtype)
-    post = py_utils.MatmulBias(ctx, theta.post_w,
-                               theta.post_b if p.use_bias else None)
-    if paddings is not None:
-      post = py_utils.ApplyPadding(paddings, post)
-    return post
+    return num / den.unsqueeze(-1)
 
 
 class BlockSparseAttention(attention_lib.MultiHeadedAttention):

@@ -239,6 +239,19 @@ std::vector<torch::Tensor> xl_attn_bwd(torch::Tensor dout, torch::Tensor q,
                                        c10::optional<torch::Tensor> klen,
                                        bool causal, double scale);
 
+// favor_attn.hip
+std::vector<torch::Tensor> favor_attn_fwd(torch::Tensor q, torch::Tensor k,
+                                          torch::Tensor v, torch::Tensor proj,
+                                          c10::optional<torch::Tensor> klen,
+                                          bool causal);
+std::vector<torch::Tensor> favor_attn_bwd(torch::Tensor dout, torch::Tensor q,
+                                          torch::Tensor k, torch::Tensor v,
+                                          torch::Tensor proj, torch::Tensor o,
+                                          torch::Tensor den,
+                                          torch::Tensor kstab,
+                                          c10::optional<torch::Tensor> klen,
+                                          bool causal);
+
 // rnnt.hip
 std::vector<torch::Tensor> rnnt_fwd(torch::Tensor logits,
                                     torch::Tensor logit_lengths,
@@ -375,6 +388,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Transformer-XL relative attention forward: o, lse");
   m.def("xl_attn_bwd", &xl_attn_bwd,
         "Transformer-XL relative attention backward: dq, dk, dv, dr, du, dw");
+  m.def("favor_attn_fwd", &favor_attn_fwd,
+        "FAVOR+ linear attention forward: o, den, key stabiliser");
+  m.def("favor_attn_bwd", &favor_attn_bwd,
+        "FAVOR+ linear attention backward: dq, dk, dv");
   m.def("rnnt_fwd", &rnnt_fwd,
         "Transducer loss forward: nll, valid and the backward's workspaces");
   m.def("rnnt_bwd", &rnnt_bwd, "Transducer loss backward: dlogits");
