@@ -15,18 +15,24 @@ ACT_CODES = {'NONE': 0, 'SILU': 1, 'SWISH': 1}
 class _GroupNormFn(torch.autograd.Function):
 
   @staticmethod
-  def forward(ctx, x, gamma, beta, paddings, groups, eps, act):
+  def forward(ctx, x, gamma, beta, paddings, groups, eps, act, route):
     ext = _loader.get_ext(required=True)
+    if route == 'auto' and ext.group_norm_tile_supported(
+        x.shape[1], x.shape[2], groups):
+      # Decided once for both directions: T fits the forward and the
+      # backward tile.
+      route = 'tile'
     pad_b = None if paddings is None else \
         paddings.to(torch.bfloat16).contiguous()
     gamma_b = gamma.to(torch.bfloat16).contiguous()
     beta_b = beta.to(torch.bfloat16).contiguous()
     y, mean, rstd = ext.group_norm_fwd(
-        x, gamma_b, beta_b, pad_b, groups, eps, act)
+        x, gamma_b, beta_b, pad_b, groups, eps, act, route)
     ctx.save_for_backward(x, gamma_b, beta_b, mean, rstd,
                           pad_b if pad_b is not None else torch.empty(0))
     ctx.groups = groups
     ctx.act = act
+    ctx.route = route
     ctx.pdtype = gamma.dtype
     return y
 
@@ -37,17 +43,24 @@ class _GroupNormFn(torch.autograd.Function):
     pad = pad_b if pad_b.numel() else None
     dx, dgamma, dbeta = ext.group_norm_bwd(
         dy.contiguous().to(torch.bfloat16), x, gamma_b, beta_b, pad,
-        mean, rstd, ctx.groups, ctx.act)
+        mean, rstd, ctx.groups, ctx.act, ctx.route)
     return (dx, dgamma.to(ctx.pdtype), dbeta.to(ctx.pdtype), None, None,
-            None, None)
+            None, None, None)
 
 
 def group_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
                paddings: Optional[torch.Tensor], groups: int,
-               eps: float = 1e-3, act: str = 'NONE') -> torch.Tensor:
+               eps: float = 1e-3, act: str = 'NONE',
+               route: str = 'auto') -> torch.Tensor:
   """Fused padded GroupNorm; act='SILU' applies swish INSIDE the same
-  kernel (fwd epilogue; bwd folds silu' without storing extra state)."""
+  kernel (fwd epilogue; bwd folds silu' without storing extra state).
+
+  route: 'auto' takes the tile-resident kernels ('tile') in both directions
+  where the group width and T allow it and the extension's own 'auto'
+  otherwise; 'vec' and 'tile' force one route in both directions."""
+  assert route in ('auto', 'vec', 'tile'), route
   orig = x.dtype
   y = _GroupNormFn.apply(x.to(torch.bfloat16).contiguous(), gamma, beta,
-                         paddings, groups, eps, ACT_CODES[act.upper()])
+                         paddings, groups, eps, ACT_CODES[act.upper()],
+                         route)
   return y.to(orig) if orig != torch.bfloat16 else y

@@ -105,7 +105,10 @@ std::vector<torch::Tensor> group_norm_bwd(torch::Tensor dy, torch::Tensor x,
                                           c10::optional<torch::Tensor> pad,
                                           torch::Tensor mean,
                                           torch::Tensor rstd,
-                                          int64_t groups, int64_t act);
+                                          int64_t groups, int64_t act,
+                                          const std::string& route);
+int64_t group_norm_tile_max_rows(bool backward);
+bool group_norm_tile_supported(int64_t T, int64_t D, int64_t groups);
 
 // lstm_gates.hip
 std::vector<torch::Tensor> lstm_gates_fwd_op(torch::Tensor gates,
@@ -285,7 +288,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("pad"),
         py::arg("groups"), py::arg("eps"), py::arg("act"),
         py::arg("route") = "auto");
-  m.def("group_norm_bwd", &group_norm_bwd, "Fused padded GroupNorm bwd");
+  m.def("group_norm_bwd", &group_norm_bwd, "Fused padded GroupNorm bwd",
+        py::arg("dy"), py::arg("x"), py::arg("gamma"), py::arg("beta"),
+        py::arg("pad"), py::arg("mean"), py::arg("rstd"), py::arg("groups"),
+        py::arg("act"), py::arg("route") = "auto");
+  m.def("group_norm_tile_max_rows", &group_norm_tile_max_rows,
+        "Largest T the tile-resident GroupNorm kernel of one direction holds "
+        "in LDS on the current device",
+        py::arg("backward"));
+  m.def("group_norm_tile_supported", &group_norm_tile_supported,
+        "Whether group_norm route='tile' serves (T, D, groups), forward and "
+        "backward",
+        py::arg("T"), py::arg("D"), py::arg("groups"));
   m.def("lstm_gates_fwd", &lstm_gates_fwd_op, "Fused LSTM gates fwd");
   m.def("lstm_gates_bwd", &lstm_gates_bwd_op, "Fused LSTM gates bwd");
   m.def("dropout_fwd", &dropout_fwd, "Fused dropout fwd");

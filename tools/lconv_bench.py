@@ -9,7 +9,12 @@ includes everything the route launches. Prints per-route median and min
 over the median, to set against the ~6.3 TB/s achievable on one MI355X.
 
   plain fwd / bwd   depthwise_conv1d kernels, route 'naive' vs 'tiled'
-  gn_fwd            GroupNorm + SiLU forward, scalar vs vector kernel
+  gn_fwd            GroupNorm + SiLU forward: scalar, vector and tile-resident
+                    kernels, beside a LayerNorm forward on the same tensor
+                    (the bandwidth yardstick: same bytes, whole rows)
+  gn_bwd            GroupNorm + SiLU backward, vector vs tile-resident kernel
+                    (each with everything it launches: fills and atomics, or
+                    the partial reduce), beside the same LayerNorm forward
   front fwd / bwd   F.glu -> ApplyPadding -> conv(naive) -> autograd GLU
                     backward, mask and bf16 column sum, against the fused
                     glu_dwconv1d kernels
@@ -87,10 +92,23 @@ def main():
 
   gamma = torch.randn(D, **bf) * 0.1
   beta = torch.randn(D, **bf) * 0.1
-  ab('gn_fwd (G=32, SiLU)',
-     {r: (lambda r=r: ext.group_norm_fwd(x, gamma, beta, padb, 32, 1e-3, 1,
-                                         r)) for r in ('scalar', 'vec')},
-     args.rounds, args.iters, {r: gb(3 * n * D) for r in ('scalar', 'vec')})
+  # Needed bytes: x in, y out (fwd); x and dy in, dx out (bwd). ln_fwd
+  # moves the forward's bytes in whole rows and is the rate to set both
+  # against.
+  ln = lambda: ext.layer_norm_fwd(x, gamma, beta, 1e-3, False)
+  fwd_routes = ('scalar', 'vec', 'tile')
+  fns = {r: (lambda r=r: ext.group_norm_fwd(x, gamma, beta, padb, 32, 1e-3, 1,
+                                            r)) for r in fwd_routes}
+  fns['ln_fwd'] = ln
+  ab('gn_fwd (G=32, SiLU)', fns, args.rounds, args.iters,
+     {r: gb(2 * n * D) for r in fns})
+  _, mean, rstd = ext.group_norm_fwd(x, gamma, beta, padb, 32, 1e-3, 1, 'vec')
+  fns = {r: (lambda r=r: ext.group_norm_bwd(dy, x, gamma, beta, padb, mean,
+                                            rstd, 32, 1, r))
+         for r in ('vec', 'tile')}
+  fns['ln_fwd'] = ln
+  ab('gn_bwd (G=32, SiLU; dx + dgamma + dbeta)', fns, args.rounds, args.iters,
+     {'vec': gb(3 * n * D), 'tile': gb(3 * n * D), 'ln_fwd': gb(2 * n * D)})
 
   def UnfusedFwd():
     u = py_utils.ApplyPadding(padf, F.glu(h, dim=-1))
