@@ -1,5 +1,5 @@
 """Efficient attention variants: chunkwise, routing (k-means sparse),
-and Performer/FAVOR+ linear attention.
+Performer/FAVOR+ linear attention and block-sparse attention.
 
 MI355X-native re-implementations of the reference's long-sequence
 attention family (lingvo/core/batch_major_attention.py:
@@ -14,7 +14,10 @@ runs dense attention). Performer replaces softmax with a random-feature
 kernel and has kernels of its own: bf16 CUDA tensors run the chunked
 linear-attention scan of ops/favor_attn.py, with the feature map fused in
 and no [B,T,N,m] or [B,T,N,m,H] tensor; elsewhere it is composed torch, two
-GEMMs (prefix sums when causal).
+GEMMs (prefix sums when causal). Block-sparse attention has kernels of its
+own too: bf16 CUDA tensors walk per-tile key lists in ops/block_sparse_attn.py
+(64-token tiles, block sizes that are multiples of 64); elsewhere, and for
+smaller blocks, it is the composed dense-mask form in fp32.
 """
 
 from __future__ import annotations
@@ -28,6 +31,7 @@ import torch.nn.functional as F
 from lingvo_amd.core import py_utils
 from lingvo_amd.core.nested_map import NestedMap
 from lingvo_amd.layers import attention as attention_lib
+from lingvo_amd.ops import block_sparse_attn
 from lingvo_amd.ops import favor_attn
 from lingvo_amd.ops import flash_attn
 
@@ -283,9 +287,18 @@ class BlockSparseAttention(attention_lib.MultiHeadedAttention):
   """Attention under a fixed block-level visibility pattern (reference
   self_attention_layer.py:30 BlockSparseAttention): queries in block i
   attend keys in block j iff block_mask[i][j]. Patterns like
-  local+global land as small boolean matrices; on GPU the masked
-  blocks are skipped by the flash kernel's tile loop (round 2), the
-  dense-mask fp32 form below is the oracle."""
+  local+global land as small boolean matrices. Tokens past the mask's
+  extent use its last block row / column.
+
+  Two routes, chosen by `block_sparse_impl` and the projected tensors: bf16
+  CUDA tensors with dim_per_head 64 or 128, a block_size that is a multiple
+  of 64 and a block_mask run, under block_sparse_impl='auto', the gfx950
+  kernels of ops/block_sparse_attn.py, which walk per-tile lists of the
+  visible 64x64 tiles: masked tiles cost neither work nor memory, forward
+  or backward. Everything else - CPU, other dtypes, head dims or block
+  sizes, block_mask=None, block_sparse_impl='torch' - runs the composed
+  dense-mask form in fp32, which materializes [B,N,T,T] logits, mask and
+  probabilities."""
 
   @classmethod
   def Params(cls):
@@ -294,8 +307,21 @@ class BlockSparseAttention(attention_lib.MultiHeadedAttention):
     p.Define('block_mask', None,
              'Nested list / tensor [nq_blocks, nk_blocks] of 0/1; '
              'None = full attention.')
+    p.Define('block_sparse_impl', 'auto',
+             "Attention-core route: 'auto' (HIP kernels on bf16 CUDA with "
+             "dim_per_head 64 or 128, block_size % 64 == 0 and a "
+             "block_mask, composed torch elsewhere) or 'torch' (always "
+             "composed).")
     p.cls = cls
     return p
+
+  def __init__(self, params):
+    super().__init__(params)
+    assert self.p.block_sparse_impl in ('auto', 'torch'), \
+        self.p.block_sparse_impl
+    # The kernel route's host-side pattern per number of blocks: the
+    # nested list is converted once, not on every FProp.
+    self._host_masks = {}
 
   def FProp(self, theta: NestedMap, query_vec: torch.Tensor,
             paddings: Optional[torch.Tensor] = None,
@@ -306,6 +332,40 @@ class BlockSparseAttention(attention_lib.MultiHeadedAttention):
     n, h = self._n, self._h
     assert self._nkv == n
     q, k, v = self._Project(theta, query_vec)
+    if (p.block_sparse_impl == 'auto' and q.is_cuda and
+        q.dtype == torch.bfloat16 and p.block_mask is not None and
+        block_sparse_attn.kernel_supports(h, p.block_size)):
+      ctx = self._KernelContext(q, k, v, paddings)
+    else:
+      ctx = self._ComposedContext(q, k, v, paddings)
+    ctx = ctx.reshape(b, t, n * h).to(query_vec.dtype)
+    post = py_utils.MatmulBias(ctx, theta.post_w,
+                               theta.post_b if p.use_bias else None)
+    if paddings is not None:
+      post = py_utils.ApplyPadding(paddings, post)
+    return post
+
+  def _KernelContext(self, q, k, v, paddings):
+    """[B,T,N,H] context vectors from ops/block_sparse_attn.py."""
+    p = self.p
+    nb = -(-q.shape[1] // p.block_size)
+    bm = self._host_masks.get(nb)
+    if bm is None:
+      bm = torch.as_tensor(p.block_mask).cpu() != 0
+      # Tokens past the mask's extent use its last block row / column.
+      blk = torch.arange(nb)
+      bm = bm[blk.clamp(max=bm.shape[0] - 1)][:,
+                                               blk.clamp(max=bm.shape[1] - 1)]
+      self._host_masks[nb] = bm
+    klen = (py_utils.LengthsFromPaddings(paddings).to(torch.int32)
+            if paddings is not None else None)
+    return block_sparse_attn.block_sparse_attention(
+        q, k, v, bm, p.block_size, klen=klen, causal=p.causal)
+
+  def _ComposedContext(self, q, k, v, paddings):
+    """[B,T,N,H] context vectors from the dense-mask form in fp32."""
+    p = self.p
+    b, t, _, h = q.shape
     scale = 1.0 / math.sqrt(h)
     logits = torch.einsum('btnh,bsnh->bnts', q.float(),
                           k.float()) * scale
@@ -326,13 +386,7 @@ class BlockSparseAttention(attention_lib.MultiHeadedAttention):
     probs = torch.softmax(logits, dim=-1)
     probs = torch.where(mask4.any(-1, keepdim=True), probs,
                         torch.zeros_like(probs))
-    ctx = torch.einsum('bnts,bsnh->btnh', probs, v.float())
-    ctx = ctx.reshape(b, t, n * h).to(query_vec.dtype)
-    post = py_utils.MatmulBias(ctx, theta.post_w,
-                               theta.post_b if p.use_bias else None)
-    if paddings is not None:
-      post = py_utils.ApplyPadding(paddings, post)
-    return post
+    return torch.einsum('bnts,bsnh->btnh', probs, v.float())
 
 
 def LocalGlobalBlockMask(num_blocks: int, num_global: int = 1,

@@ -255,6 +255,22 @@ std::vector<torch::Tensor> favor_attn_bwd(torch::Tensor dout, torch::Tensor q,
                                           c10::optional<torch::Tensor> klen,
                                           bool causal);
 
+// block_sparse_attn.hip
+std::vector<torch::Tensor> bsa_fwd(torch::Tensor q, torch::Tensor k,
+                                   torch::Tensor v,
+                                   c10::optional<torch::Tensor> klen,
+                                   torch::Tensor q_ptr, torch::Tensor q_cols,
+                                   torch::Tensor q_order, bool causal,
+                                   double scale);
+std::vector<torch::Tensor> bsa_bwd(torch::Tensor dout, torch::Tensor q,
+                                   torch::Tensor k, torch::Tensor v,
+                                   torch::Tensor o, torch::Tensor lse,
+                                   c10::optional<torch::Tensor> klen,
+                                   torch::Tensor q_ptr, torch::Tensor q_cols,
+                                   torch::Tensor q_order, torch::Tensor k_ptr,
+                                   torch::Tensor k_rows, torch::Tensor k_order,
+                                   bool causal, double scale);
+
 // rnnt.hip
 std::vector<torch::Tensor> rnnt_fwd(torch::Tensor logits,
                                     torch::Tensor logit_lengths,
@@ -406,6 +422,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "FAVOR+ linear attention forward: o, den, key stabiliser");
   m.def("favor_attn_bwd", &favor_attn_bwd,
         "FAVOR+ linear attention backward: dq, dk, dv");
+  m.def("bsa_fwd", &bsa_fwd,
+        "Block-sparse attention forward over per-tile key lists: o, lse");
+  m.def("bsa_bwd", &bsa_bwd, "Block-sparse attention backward: dq, dk, dv");
   m.def("rnnt_fwd", &rnnt_fwd,
         "Transducer loss forward: nll, valid and the backward's workspaces");
   m.def("rnnt_bwd", &rnnt_bwd, "Transducer loss backward: dlogits");
