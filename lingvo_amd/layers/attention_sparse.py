@@ -8,9 +8,12 @@ attention_util.py:656 KMeansClusteringForAtten; favor_attention.py
 FAVOR+). All share MultiHeadedAttention's projections and FProp
 surface, so they are drop-in `atten_tpl` choices.
 
-Chunkwise runs its mask inside the flash kernel; routing reshapes the
-problem rather than the kernel (it gathers per-cluster key subsets, then
-runs dense attention). Performer replaces softmax with a random-feature
+Chunkwise runs its mask inside the flash kernel. Routing has kernels of its
+own: bf16 CUDA tensors build per-cluster query and key lists on the device
+and walk them in 64x64 tiles (ops/routing_attn.py), so a query costs its own
+cluster's keys only; elsewhere it is the composed per-cluster loop in fp32
+(topk, gather, dense attention of all queries against each cluster's keys).
+Performer replaces softmax with a random-feature
 kernel and has kernels of its own: bf16 CUDA tensors run the chunked
 linear-attention scan of ops/favor_attn.py, with the feature map fused in
 and no [B,T,N,m] or [B,T,N,m,H] tensor; elsewhere it is composed torch, two
@@ -34,6 +37,7 @@ from lingvo_amd.layers import attention as attention_lib
 from lingvo_amd.ops import block_sparse_attn
 from lingvo_amd.ops import favor_attn
 from lingvo_amd.ops import flash_attn
+from lingvo_amd.ops import routing_attn
 
 
 class ChunkwiseSelfAttention(attention_lib.MultiHeadedAttention):
@@ -81,7 +85,16 @@ class RoutingAttention(attention_lib.MultiHeadedAttention):
   batch_major_attention.py:4458): queries attend only to the
   `atten_window` keys nearest (by cluster) to them. Per-head centroids
   are EMA-updated buffers; queries/keys are routed to their nearest
-  centroid and attention runs within each cluster's gathered key set."""
+  centroid and attention runs within each cluster's gathered key set.
+
+  Two routes, chosen by `routing_impl` and the projected tensors: bf16 CUDA
+  tensors with dim_per_head 64 or 128 and at most 64 clusters run, under
+  routing_impl='auto', the gfx950 kernels of ops/routing_attn.py, which sort
+  the queries by cluster and gather each cluster's keys on the device: a
+  query meets its own cluster's keys only, forward and backward. Everything
+  else - CPU, other dtypes or head dims, routing_impl='torch' - runs the
+  composed loop over the clusters in fp32, which attends all queries to
+  every cluster's keys and keeps the one-hot selected part."""
 
   @classmethod
   def Params(cls):
@@ -89,12 +102,17 @@ class RoutingAttention(attention_lib.MultiHeadedAttention):
     p.Define('num_clusters', 4, 'k-means clusters per head.')
     p.Define('atten_window', 64, 'Keys gathered per cluster (capacity).')
     p.Define('decay', 0.999, 'Centroid EMA decay.')
+    p.Define('routing_impl', 'auto',
+             "Attention-core route: 'auto' (HIP kernels on bf16 CUDA with "
+             "dim_per_head 64 or 128 and num_clusters <= 64, composed torch "
+             "elsewhere) or 'torch' (always composed).")
     p.cls = cls
     return p
 
   def __init__(self, params):
     super().__init__(params)
     p = self.p
+    assert p.routing_impl in ('auto', 'torch'), p.routing_impl
     self.register_buffer('centroids', torch.randn(
         self._n, p.num_clusters, self._h) * (1.0 / math.sqrt(self._h)))
 
@@ -127,11 +145,41 @@ class RoutingAttention(attention_lib.MultiHeadedAttention):
           target = alive * mean + (1 - alive) * self.centroids[:, c]
           self.centroids[:, c] = (p.decay * self.centroids[:, c] +
                                   (1 - p.decay) * target)
+    ctx = self._Context(q, k, v, q_cl, k_cl, paddings)
+    ctx = ctx.reshape(b, t, n * h).to(query_vec.dtype)
+    post = py_utils.MatmulBias(ctx, theta.post_w,
+                               theta.post_b if p.use_bias else None)
+    if paddings is not None:
+      post = py_utils.ApplyPadding(paddings, post)
+    return post
+
+  def _Context(self, q, k, v, q_cl, k_cl, paddings):
+    """[B,T,N,H] context vectors by the route of `routing_impl`."""
+    p = self.p
+    if (p.routing_impl == 'auto' and q.is_cuda and
+        q.dtype == torch.bfloat16 and
+        routing_attn.kernel_supports(self._h, p.num_clusters)):
+      return self._KernelContext(q, k, v, q_cl, k_cl, paddings)
+    return self._ComposedContext(q, k, v, q_cl, k_cl, paddings)
+
+  def _KernelContext(self, q, k, v, q_cl, k_cl, paddings):
+    """[B,T,N,H] context vectors from ops/routing_attn.py."""
+    p = self.p
+    return routing_attn.routing_attention(
+        q, k, v, q_cl, k_cl, p.num_clusters, p.atten_window,
+        paddings=paddings, causal=p.causal)
+
+  def _ComposedContext(self, q, k, v, q_cl, k_cl, paddings):
+    """[B,T,N,H] context vectors from the loop over the clusters in fp32
+    (fp64 for fp64 inputs)."""
+    p = self.p
+    b, t, n, h = q.shape
+    ft = torch.float64 if q.dtype == torch.float64 else torch.float32
     wnd = min(p.atten_window, t)
     kpad = paddings if paddings is not None else torch.zeros(
         b, t, device=q.device)
-    out = torch.zeros(b, t, n, h, dtype=torch.float32, device=q.device)
-    qf, kf, vf = q.float(), k.float(), v.float()
+    out = torch.zeros(b, t, n, h, dtype=ft, device=q.device)
+    qf, kf, vf = q.to(ft), k.to(ft), v.to(ft)
     scale = 1.0 / math.sqrt(h)
     for c in range(p.num_clusters):
       # scores for membership: keys in cluster c, unpadded
@@ -157,14 +205,9 @@ class RoutingAttention(attention_lib.MultiHeadedAttention):
       all_masked = (logits.max(-1, keepdim=True).values < -1e29)
       probs = probs.masked_fill(all_masked, 0.0)
       ctx = torch.einsum('bntw,bnwh->btnh', probs, vg)
-      sel = (q_cl == c).permute(0, 2, 1).unsqueeze(-1).float()
+      sel = (q_cl == c).permute(0, 2, 1).unsqueeze(-1).to(ft)
       out = out + ctx * sel
-    ctx = out.reshape(b, t, n * h).to(query_vec.dtype)
-    post = py_utils.MatmulBias(ctx, theta.post_w,
-                               theta.post_b if p.use_bias else None)
-    if paddings is not None:
-      post = py_utils.ApplyPadding(paddings, post)
-    return post
+    return out
 
 
 class PerformerAttention(attention_lib.MultiHeadedAttention):

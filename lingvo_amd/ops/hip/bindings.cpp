@@ -271,6 +271,25 @@ std::vector<torch::Tensor> bsa_bwd(torch::Tensor dout, torch::Tensor q,
                                    torch::Tensor k_rows, torch::Tensor k_order,
                                    bool causal, double scale);
 
+// routing_attn.hip
+int64_t routing_max_clusters();
+std::vector<torch::Tensor> routing_lists(torch::Tensor q, torch::Tensor k,
+                                         torch::Tensor v, torch::Tensor q_cl,
+                                         torch::Tensor k_cl,
+                                         c10::optional<torch::Tensor> live,
+                                         int64_t num_clusters,
+                                         int64_t window);
+std::vector<torch::Tensor> routing_attn_fwd(torch::Tensor q, torch::Tensor k,
+                                            torch::Tensor v,
+                                            std::vector<torch::Tensor> lists,
+                                            int64_t num_clusters,
+                                            int64_t window, bool causal,
+                                            double scale);
+std::vector<torch::Tensor> routing_attn_bwd(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor o, torch::Tensor lse, std::vector<torch::Tensor> lists,
+    int64_t num_clusters, int64_t window, bool causal, double scale);
+
 // rnnt.hip
 std::vector<torch::Tensor> rnnt_fwd(torch::Tensor logits,
                                     torch::Tensor logit_lengths,
@@ -425,6 +444,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bsa_fwd", &bsa_fwd,
         "Block-sparse attention forward over per-tile key lists: o, lse");
   m.def("bsa_bwd", &bsa_bwd, "Block-sparse attention backward: dq, dk, dv");
+  m.def("routing_max_clusters", &routing_max_clusters,
+        "Largest num_clusters the routing attention kernels support");
+  m.def("routing_lists", &routing_lists,
+        "Routing attention lists, built on the device: q_perm, q_start, "
+        "q_tiles, q_ntiles, k_sel, k_cnt");
+  m.def("routing_attn_fwd", &routing_attn_fwd,
+        "Routing attention forward over the gathered key lists: o, lse");
+  m.def("routing_attn_bwd", &routing_attn_bwd,
+        "Routing attention backward: dq, dk, dv");
   m.def("rnnt_fwd", &rnnt_fwd,
         "Transducer loss forward: nll, valid and the backward's workspaces");
   m.def("rnnt_bwd", &rnnt_bwd, "Transducer loss backward: dlogits");

@@ -52,22 +52,9 @@
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 
-#include "attn_tile.h"
+#include "sparse_tile.h"
 
 namespace {
-
-constexpr int BT = 64;                  // tile edge, queries and keys
-constexpr int BNW = 4;                  // waves per block
-constexpr int BBLOCK = BNW * WAVE_SIZE;
-constexpr int TP = BT * 2;              // byte pitch of a [.][64] bf16 tile
-constexpr int NF = BT / 16;             // 16-wide fragments across a tile
-
-// A 64 x H tile in flight between global memory and LDS: H/8 threads per
-// row, 16 bytes each, H/32 passes of 2048/H rows.
-template <int H>
-struct TileRegs {
-  ushortx8 v[H / 32];
-};
 
 // Rows >= valid are zeros.
 template <int H>
@@ -90,36 +77,6 @@ __device__ __forceinline__ void tile_load(const unsigned short* src,
   }
 }
 
-// -> LDS row-major [64][H], swizzled.
-template <int H>
-__device__ __forceinline__ void tile_put_rows(const TileRegs<H>& t,
-                                              char* dst) {
-  constexpr int TPR = H / 8, RPP = BBLOCK / TPR;
-  const int r0 = threadIdx.x / TPR;
-  const int h0 = (threadIdx.x % TPR) * 8;
-#pragma unroll
-  for (int rp = 0; rp < H / 32; ++rp) {
-    const int row = r0 + rp * RPP;
-    *reinterpret_cast<ushortx8*>(dst + row * (H * 2) + swz(row, h0 * 2)) =
-        t.v[rp];
-  }
-}
-
-// -> LDS transposed [H][64], swizzled per h-row.
-template <int H>
-__device__ __forceinline__ void tile_put_transposed(const TileRegs<H>& t,
-                                                    char* dst) {
-  constexpr int TPR = H / 8, RPP = BBLOCK / TPR;
-  const int r0 = threadIdx.x / TPR;
-  const int h0 = (threadIdx.x % TPR) * 8;
-#pragma unroll
-  for (int rp = 0; rp < H / 32; ++rp) {
-    const int row = r0 + rp * RPP;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lds_put(dst, h0 + j, TP, row, t.v[rp][j]);
-  }
-}
-
 // A-operand fragments of one 16-row strip of x [.,H]: row = row0 + (lane&15),
 // zeros from row `limit` on.
 template <int H>
@@ -137,21 +94,6 @@ __device__ __forceinline__ void load_strip(const unsigned short* x,
       const float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       frag[kk] = pack_bf16x8(z);
     }
-  }
-}
-
-// One wave's [16][64] fp32 strip in C layout (row g*4+r, col nf*16+cl) into
-// its LDS strip as bf16 MFMA A operands.
-__device__ __forceinline__ void strip_to_lds(const float (&s)[NF][4],
-                                             float mul, char* pw) {
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4, cl = lane & 15;
-#pragma unroll
-  for (int nf = 0; nf < NF; ++nf) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      lds_put(pw, g * 4 + r, TP, nf * 16 + cl,
-              float_to_bf16_bits(s[nf][r] * mul));
   }
 }
 
@@ -619,39 +561,15 @@ struct BsaShape {
   long sq, sk, sv;
 };
 
-// Stride contract of q, k and v: bf16 [B,T,N,H] whose [N][H] dims are dense,
-// whose token rows (b, t) sit at one uniform stride that is a multiple of 8
-// elements and at least N*H, and whose base is 16-byte aligned. Returns the
-// row stride in elements.
-long bsa_row_stride(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.dim() == 4 &&
-                  t.scalar_type() == torch::kBFloat16,
-              "block_sparse_attn: ", name,
-              " must be a CUDA bf16 [B,T,N,H] tensor");
-  const long B = t.size(0), T = t.size(1), N = t.size(2), H = t.size(3);
-  TORCH_CHECK(t.stride(3) == 1 && (N == 1 || t.stride(2) == H),
-              "block_sparse_attn: ", name, ": the [N][H] dims must be dense");
-  const long row = T > 1 ? t.stride(1) : (B > 1 ? t.stride(0) : N * H);
-  TORCH_CHECK(B == 1 || T == 1 || t.stride(0) == T * row,
-              "block_sparse_attn: ", name,
-              ": batch stride must be T * row stride");
-  TORCH_CHECK(row % 8 == 0 && row >= N * H, "block_sparse_attn: ", name,
-              ": row stride must be a multiple of 8 elements and >= N*H, got ",
-              row);
-  TORCH_CHECK(aligned16(t), "block_sparse_attn: ", name,
-              ": base pointer must be 16-byte aligned");
-  return row;
-}
-
 BsaShape bsa_check(const torch::Tensor& q, const torch::Tensor& k,
                    const torch::Tensor& v,
                    const c10::optional<torch::Tensor>& klen,
                    const torch::Tensor& ptr, const torch::Tensor& idx,
                    const torch::Tensor& order) {
   BsaShape s;
-  s.sq = bsa_row_stride(q, "q");
-  s.sk = bsa_row_stride(k, "k");
-  s.sv = bsa_row_stride(v, "v");
+  s.sq = check_token_rows(q, "block_sparse_attn", "q");
+  s.sk = check_token_rows(k, "block_sparse_attn", "k");
+  s.sv = check_token_rows(v, "block_sparse_attn", "v");
   s.B = q.size(0), s.T = q.size(1), s.N = q.size(2), s.H = q.size(3);
   TORCH_CHECK(s.H == 64 || s.H == 128,
               "block_sparse_attn: H must be 64 or 128, got ", s.H);

@@ -50,3 +50,26 @@ inline void check_dense(const torch::Tensor& t, torch::ScalarType st,
   TORCH_CHECK(cuda_rows(t, st, rows, cols) && aligned16(t), name,
               " must be a dense CUDA [", rows, ",", cols, "] tensor of ", st);
 }
+
+// Stride contract of the q, k and v of the list-walking attention ops: bf16
+// [B,T,N,H] whose [N][H] dims are dense, whose token rows (b, t) sit at one
+// uniform stride that is a multiple of 8 elements and at least N*H, and whose
+// base is 16-byte aligned. Returns the row stride in elements.
+inline long check_token_rows(const torch::Tensor& t, const char* op,
+                             const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 &&
+                  t.scalar_type() == torch::kBFloat16,
+              op, ": ", name, " must be a CUDA bf16 [B,T,N,H] tensor");
+  const long B = t.size(0), T = t.size(1), N = t.size(2), H = t.size(3);
+  TORCH_CHECK(t.stride(3) == 1 && (N == 1 || t.stride(2) == H), op, ": ",
+              name, ": the [N][H] dims must be dense");
+  const long row = T > 1 ? t.stride(1) : (B > 1 ? t.stride(0) : N * H);
+  TORCH_CHECK(B == 1 || T == 1 || t.stride(0) == T * row, op, ": ", name,
+              ": batch stride must be T * row stride");
+  TORCH_CHECK(row % 8 == 0 && row >= N * H, op, ": ", name,
+              ": row stride must be a multiple of 8 elements and >= N*H, got ",
+              row);
+  TORCH_CHECK(aligned16(t), op, ": ", name,
+              ": base pointer must be 16-byte aligned");
+  return row;
+}
