@@ -71,11 +71,12 @@ class _FlashAttnFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, q, k, v, klen, bias, qseg, kseg, win_l, win_r,
-              bias_clip, scale, chunk_size, left_chunks, bwd_route='auto'):
+              bias_clip, scale, chunk_size, left_chunks, bwd_route='auto',
+              fwd_route='auto'):
     ext = _loader.get_ext(required=True)
     bias_b = None if bias is None else bias.to(torch.bfloat16).contiguous()
     o, lse = ext.fa_fwd(q, k, v, klen, bias_b, qseg, kseg, win_l, win_r,
-                        bias_clip, scale, chunk_size, left_chunks)
+                        bias_clip, scale, chunk_size, left_chunks, fwd_route)
     empty = torch.empty(0)
     ctx.bwd_route = bwd_route
     ctx.save_for_backward(q, k, v, o, lse,
@@ -104,7 +105,7 @@ class _FlashAttnFn(torch.autograd.Function):
         left_chunks, route=ctx.bwd_route)
     dbias_out = dbias.to(bias_dtype) if bias_grad else None
     return (dq, dk, dv, None, dbias_out, None, None, None, None, None,
-            None, None, None, None)
+            None, None, None, None, None)
 
 
 class _FlashAttnPackedFn(torch.autograd.Function):
@@ -119,13 +120,14 @@ class _FlashAttnPackedFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, qkv, n, h, klen, bias, qseg, kseg, win_l, win_r,
-              bias_clip, scale, chunk_size, left_chunks, bwd_route='auto'):
+              bias_clip, scale, chunk_size, left_chunks, bwd_route='auto',
+              fwd_route='auto'):
     ext = _loader.get_ext(required=True)
     ctx.bwd_route = bwd_route
     bias_b = None if bias is None else bias.to(torch.bfloat16).contiguous()
     q, k, v = _FlashAttnPackedFn._views(qkv, n, h)
     o, lse = ext.fa_fwd(q, k, v, klen, bias_b, qseg, kseg, win_l, win_r,
-                        bias_clip, scale, chunk_size, left_chunks)
+                        bias_clip, scale, chunk_size, left_chunks, fwd_route)
     empty = torch.empty(0)
     ctx.save_for_backward(qkv, o, lse,
                           klen if klen is not None else empty,
@@ -156,7 +158,7 @@ class _FlashAttnPackedFn(torch.autograd.Function):
         left_chunks, dq, dk, dv, ctx.bwd_route)[3]
     dbias_out = dbias.to(bias_dtype) if bias_grad else None
     return (dqkv, None, None, None, dbias_out, None, None, None, None,
-            None, None, None, None, None)
+            None, None, None, None, None, None)
 
 
 def flash_attention_packed(qkv: torch.Tensor, num_heads: int,
@@ -168,11 +170,12 @@ def flash_attention_packed(qkv: torch.Tensor, num_heads: int,
                            q_segment_ids: Optional[torch.Tensor] = None,
                            k_segment_ids: Optional[torch.Tensor] = None,
                            chunk_size: int = 0, left_chunks: int = 0,
-                           bwd_route: str = 'auto') -> torch.Tensor:
+                           bwd_route: str = 'auto',
+                           fwd_route: str = 'auto') -> torch.Tensor:
   """flash_attention on a packed self-attention projection: qkv is
   [B,T,3*N*H] bf16 CUDA laid out [q | k | v] with N == NKV == num_heads.
   Returns o [B,T,N,H]; the gradient is one [B,T,3*N*H] tensor.
-  bwd_route forces the backward kernel (see flash_attention)."""
+  bwd_route and fwd_route force a kernel (see flash_attention)."""
   assert qkv.is_cuda and qkv.dtype == torch.bfloat16
   assert qkv.shape[-1] % (3 * num_heads) == 0
   h = qkv.shape[-1] // (3 * num_heads)
@@ -186,7 +189,7 @@ def flash_attention_packed(qkv: torch.Tensor, num_heads: int,
   return _FlashAttnPackedFn.apply(
       qkv.contiguous(), num_heads, h, klen, bias, q_segment_ids,
       k_segment_ids, win_l, win_r, bias_clip, scale, chunk_size,
-      left_chunks, bwd_route)
+      left_chunks, bwd_route, fwd_route)
 
 
 def _meets_stride_contract(t: torch.Tensor) -> bool:
@@ -219,14 +222,18 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     q_segment_ids: Optional[torch.Tensor] = None,
                     k_segment_ids: Optional[torch.Tensor] = None,
                     chunk_size: int = 0, left_chunks: int = 0,
-                    bwd_route: str = 'auto') -> torch.Tensor:
+                    bwd_route: str = 'auto',
+                    fwd_route: str = 'auto') -> torch.Tensor:
   """q [B,T,N,H], k/v [B,S,NKV,H] -> [B,T,N,H]. Optional packed-input
   segment ids [B,T]/[B,S]: attention is blocked across segments
   (reference PackSequences segment_ids consumed by the mask path).
 
   bwd_route picks the GPU backward kernel: 'auto' (by shape), 'tiles'
   (one workgroup per 128-key tile, dQ through fp32 atomics) or 'fused'
-  (one workgroup per head; raises where the shape does not qualify)."""
+  (one workgroup per head; raises where the shape does not qualify).
+  fwd_route does the same for the forward: 'tiles' (one workgroup per 128
+  queries, K and V staged per 64-key tile) or 'fused' (one workgroup per
+  head with K and V^T resident, S^T = K Q^T and P fed from registers)."""
   if scale is None:
     scale = 1.0 / math.sqrt(q.shape[-1])
   if klen is not None:
@@ -239,7 +246,7 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     out = _FlashAttnFn.apply(
         _kernel_input(q), _kernel_input(k), _kernel_input(v), klen, bias,
         q_segment_ids, k_segment_ids, win_l, win_r, bias_clip, scale,
-        chunk_size, left_chunks, bwd_route)
+        chunk_size, left_chunks, bwd_route, fwd_route)
     return out.to(orig) if orig != torch.bfloat16 else out
   out = _ref_attention(q, k, v, klen, bias, win_l, win_r, bias_clip, scale,
                        q_segment_ids, k_segment_ids, chunk_size,

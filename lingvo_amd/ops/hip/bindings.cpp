@@ -27,7 +27,8 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
                                   c10::optional<torch::Tensor> kseg,
                                   int64_t win_l, int64_t win_r,
                                   int64_t bias_clip, double scale,
-                                  int64_t chunk_size, int64_t left_chunks);
+                                  int64_t chunk_size, int64_t left_chunks,
+                                  const std::string& route);
 std::vector<torch::Tensor> fa_bwd(torch::Tensor dout, torch::Tensor q,
                                   torch::Tensor k, torch::Tensor v,
                                   torch::Tensor o, torch::Tensor lse,
@@ -368,7 +369,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rstd"), py::arg("rms"), py::arg("dres") = py::none());
   m.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 layout probe");
-  m.def("fa_fwd", &fa_fwd, "Flash attention forward");
+  m.def("fa_fwd", &fa_fwd, "Flash attention forward", py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("klen"), py::arg("bias"),
+        py::arg("qseg"), py::arg("kseg"), py::arg("win_l"), py::arg("win_r"),
+        py::arg("bias_clip"), py::arg("scale"), py::arg("chunk_size"),
+        py::arg("left_chunks"), py::arg("route") = "auto");
   m.def("fa_bwd", &fa_bwd, "Flash attention backward", py::arg("dout"),
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("klen"), py::arg("bias"), py::arg("qseg"),

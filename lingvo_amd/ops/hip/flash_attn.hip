@@ -3,8 +3,15 @@
 // AttenProbs:943 — BTNH layouts, causal/local/padding masks, clipped
 // relative-position bias, GQA).
 //
-// Structure (v1, correctness-first; guide §B "fused attention prefill"):
-//  - fwd: grid (ceil(T/128), N, B); block = 8 waves; each wave owns a
+// Structure (guide §B "fused attention prefill"):
+//  - fwd, two routes chosen on the host from shapes only:
+//    'fused' (fa_fwd_fused_kernel): self-attention with N == NKV, H == 64,
+//    T == S <= 384, no segment ids or chunkwise mask. Grid (N, B), one
+//    workgroup of 8 waves per head with K and V^T resident in LDS; S^T =
+//    K Q^T so a lane owns one query, P goes to the second MFMA from
+//    registers (see the kernel's header).
+//    'tiles' (fa_fwd_kernel, v1, correctness-first): every other shape.
+//    Grid (ceil(T/128), N, B); block = 8 waves; each wave owns a
 //    16-row Q strip. K staged in LDS row-major (XOR-swizzled) in tiles of
 //    64 keys (128 from S = 512 on), V staged transposed [H][tile]; online
 //    softmax in fp32 with per-row (m, l) tracked in the 16-lane C-layout
@@ -362,6 +369,287 @@ __global__ __launch_bounds__(FWD_BLOCK) void fa_fwd_kernel(
     if (cl == 0) {
       lse[((long)b * N + n) * T + qrow] =
           l_run[r] > 0.f ? m_run[r] + __logf(l_run[r]) : NEG_INF;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Forward, fused route: one workgroup per (head, batch), self-attention with
+// N == NKV, H == 64 and T == S <= FWD_FUSED_MAX_S.
+//
+// The head's K (row-major) and V^T are staged into LDS once; strips of 16
+// queries are dealt round-robin to the waves, and a wave walks its strip's
+// keys in steps of 64 with an online softmax.
+//
+// S^T = K Q^T: in the MFMA C layout a lane then holds one query (its column
+// cl) and keys g*4 + r of each 16-key fragment, so the row maximum and sum
+// are reductions over the lane's own registers plus the four g-lanes of a
+// query, and the rescale and 1/l are one scalar per lane. Logits are kept in
+// the base-2 domain (scale and the bias row carry log2 e).
+//
+// O^T = V^T P^T with P^T as the B operand, straight from registers: two
+// neighbouring S^T fragments give a lane the 8 k-slots of a 32-key step in
+// the order slot g*8 + hs*4 + r <-> key hs*16 + g*4 + r. The contraction is a
+// sum, so V^T is laid out in LDS in that slot order and its A fragment is one
+// 16-byte read. A lane ends with 4 consecutive h of one query.
+// ---------------------------------------------------------------------------
+constexpr int FWD_FUSED_MAX_S = 384;
+constexpr int FFK = 64;                    // keys per softmax step
+// 8 waves: two workgroups share a CU at 128 registers a wave. 10 waves deal
+// the workload's 19 strips more evenly but need 96 registers, spill, and
+// measured 1.7x slower (docs/KERNEL_NOTES.md).
+constexpr int FFW = 8;
+
+typedef __attribute__((ext_vector_type(8))) float ff_floatx8;
+typedef __attribute__((ext_vector_type(4))) __bf16 ff_bf16x4;
+
+// Swizzle of a V^T row h: as swz(), but rows 8 apart differ too, so the
+// transposed staging writes of one key group spread over the banks.
+__device__ __forceinline__ int swz_vt(int h, int byte_in_row) {
+  return byte_in_row ^ (((h ^ (h >> 3)) & 7) << 4);
+}
+
+// LDS of the fused forward: K rows padded to the 16-key strip, V^T rows of
+// whole 64-key steps, the head's bias row in fp32. A step's K fragments past
+// the last strip are read from the start of the V^T region, which is always
+// larger than the 48 rows they can reach; those keys are masked.
+static size_t fwd_fused_lds_bytes(int T, bool has_bias, int nbias) {
+  return (size_t)cdiv(T, 16) * 16 * 128 + (size_t)64 * cdiv(T, FFK) * FFK * 2 +
+         (has_bias ? nbias * sizeof(float) : 0);
+}
+
+// Registers are held to what lets two workgroups share a CU (2 * NW waves
+// over 4 SIMDs); at T = 300 the LDS request allows two as well.
+template <int NW, bool BIAS>
+__global__ __launch_bounds__(NW * WAVE_SIZE, (2 * NW + 3) / 4) void
+fa_fwd_fused_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
+    const unsigned short* __restrict__ v,
+    const int* __restrict__ klen_ptr,          // [B] or null
+    const unsigned short* __restrict__ bias,   // [N][2C+1] if BIAS
+    unsigned short* __restrict__ o, float* __restrict__ lse, int T, int N,
+    int win_l, int win_r, int bias_clip, float scale, long sq, long sk,
+    long sv) {
+  constexpr int H = 64;
+  constexpr int NT = NW * WAVE_SIZE;
+  constexpr int ROWB = H * 2;
+  constexpr int HF = H / 16;
+  constexpr int NF = FFK / 16;
+  constexpr float LOG2E = 1.4426950408889634f;
+  constexpr float LN2 = 0.6931471805599453f;
+  const int nbias = 2 * bias_clip + 1;
+  const int krows = ((T + 15) >> 4) << 4;
+  const int vpitch = ((T + FFK - 1) / FFK) * FFK * 2;  // multiple of 128
+  extern __shared__ char smem[];
+  char* k_lds = smem;                          // [krows][H] swz
+  char* vt_lds = k_lds + krows * ROWB;         // [H][slots] swz_vt
+  float* bias_s = (float*)(vt_lds + H * vpitch);  // [nbias] * log2 e if BIAS
+
+  const int n = blockIdx.x;
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int wid = tid / WAVE_SIZE;
+  const int lane = tid & 63;
+  const int g = lane >> 4;
+  const int cl = lane & 15;
+  const int klen = klen_ptr ? min(max(klen_ptr[b], 0), T) : T;
+  const int kend = ((klen + FFK - 1) / FFK) * FFK;   // keys the steps touch
+  const int wl = win_l < 0 ? 0x3fffffff : win_l;
+  const int wr = win_r < 0 ? 0x3fffffff : win_r;
+  const int nqs = (T + 15) >> 4;
+
+  // Q fragments (B layout of K Q^T): query = cl, h = kk*32 + g*8. Clamped
+  // row, never stored for rows >= T. The first strip's loads are in flight
+  // across the staging below, the next strip's across the current one.
+  bf16x8 qn[2];
+  auto load_q = [&](int qs) {
+    const long tok = (long)b * T + min(qs * 16 + cl, T - 1);
+    const unsigned short* p = q + tok * sq + n * H + g * 8;
+    qn[0] = load_bf16x8_bits(p);
+    qn[1] = load_bf16x8_bits(p + 32);
+  };
+  load_q(min(wid, nqs - 1));
+
+  // K: 16 bytes of one key row per thread. Clamped row, select at commit.
+  for (int i = tid; i < min(kend, krows) * (ROWB / 16); i += NT) {
+    const int key = i >> 3;
+    const int c = i & 7;
+    ushortx8 kv = *reinterpret_cast<const ushortx8*>(
+        k + ((long)b * T + min(key, T - 1)) * sk + n * H + c * 8);
+    const bool ok = key < klen;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) kv[j] = ok ? kv[j] : (unsigned short)0;
+    *reinterpret_cast<ushortx8*>(k_lds + key * ROWB + swz(key, c * 16)) = kv;
+  }
+  // V^T: 8 h of 4 consecutive keys per thread, which are 4 neighbouring
+  // slots: one 8-byte write per h.
+  for (int i = tid; i < (kend >> 2) * (ROWB / 16); i += NT) {
+    const int key0 = (i >> 3) * 4;
+    const int c = i & 7;
+    ushortx8 vv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      vv[r] = *reinterpret_cast<const ushortx8*>(
+          v + ((long)b * T + min(key0 + r, T - 1)) * sv + n * H + c * 8);
+    const int slotb =
+        ((key0 & ~31) + ((key0 >> 2) & 3) * 8 + ((key0 >> 4) & 1) * 4) * 2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int h = c * 8 + j;
+      ushortx4 w;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        w[r] = key0 + r < klen ? vv[r][j] : (unsigned short)0;
+      *reinterpret_cast<ushortx4*>(vt_lds + h * vpitch + swz_vt(h, slotb)) = w;
+    }
+  }
+  if (BIAS) {
+    for (int i = tid; i < nbias; i += NT)
+      bias_s[i] = bf16_bits_to_float(bias[(long)n * nbias + i]) * LOG2E;
+  }
+  __syncthreads();
+
+  const float sc2 = scale * LOG2E;
+  // Byte offsets in LDS of the first and last entry of the bias row.
+  const int bias_lo = (int)((char*)bias_s - smem);
+  const int bias_hi = bias_lo + (nbias - 1) * 4;
+  for (int qs = wid; qs < nqs; qs += NW) {
+    const bf16x8 qf0 = qn[0], qf1 = qn[1];
+    if (qs + NW < nqs) load_q(qs + NW);
+    const int q0 = qs * 16;
+    const int qcol = q0 + cl;
+
+    f32x4 acc_o[HF];
+#pragma unroll
+    for (int hf = 0; hf < HF; ++hf) acc_o[hf] = {0.f, 0.f, 0.f, 0.f};
+    float m_run = NEG_INF;   // the query's running maximum, base-2 logits
+    float l_run = 0.f;       // this lane's share of the query's sum
+
+    // Steps of 64 keys with a key some query of the strip can see.
+    const int klo = max(q0 - wl, 0);
+    const int khi = min(klen, q0 + 16 + wr);     // exclusive
+    for (int kb = klo / FFK; kb < (khi + FFK - 1) / FFK; ++kb) {
+      const int kbase = kb * FFK;
+      // Wave-uniform: no (query, key) of the step is masked.
+      const bool full = (kbase + FFK <= klen) & (kbase >= q0 + 15 - wl) &
+                        (kbase + FFK - 1 <= q0 + wr);
+      float s[NF][4];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        acc = mfma16x16x32_bf16(
+            lds_frag(k_lds, kbase + f * 16 + cl, ROWB, (g * 8) * 2), qf0, acc);
+        acc = mfma16x16x32_bf16(
+            lds_frag(k_lds, kbase + f * 16 + cl, ROWB, (32 + g * 8) * 2), qf1,
+            acc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[f][r] = acc[r];
+      }
+      // Key of s[f][r] is kbase + g*4 + c with c = f*16 + r.
+      if (BIAS) {
+        // Byte offset in LDS of the row entry of c = 0; c lowers it.
+        const int i0b = bias_lo + (qcol - kbase - g * 4 + bias_clip) * 4;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            int off;  // byte offset of the clamped row entry
+            asm("v_med3_i32 %0, %1, %2, %3"
+                : "=v"(off)
+                : "v"(i0b - (f * 16 + r) * 4), "s"(bias_lo), "v"(bias_hi));
+            s[f][r] = fmaf(s[f][r], sc2,
+                           *reinterpret_cast<const float*>(smem + off));
+          }
+        }
+      } else {
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s[f][r] *= sc2;
+        }
+      }
+      if (!full) {
+        // Visible c of this lane: [lo, lo + span).
+        const int k0 = kbase + g * 4;
+        const int lo = max(qcol - wl, 0) - k0;
+        const int span = max(min(klen - 1, qcol + wr) - k0 - lo + 1, 0);
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = f * 16 + r;
+            s[f][r] = (unsigned)(c - lo) < (unsigned)span ? s[f][r] : NEG_INF;
+          }
+        }
+      }
+      float mx = s[0][0];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[f][r]);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float m_new = fmaxf(m_run, mx);
+      // A masked logit is NEG_INF; with the subtrahend kept above it both a
+      // masked p and the alpha of a so far fully masked query come out 0.
+      const float msub = fmaxf(m_new, NEG_INF * 0.1f);
+      const float alpha = __builtin_amdgcn_exp2f(m_run - msub);
+      m_run = m_new;
+      float sum = 0.f;
+      ff_floatx8 pf[NF / 2];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(s[f][r] - msub);
+          sum += p;
+          pf[f >> 1][(f & 1) * 4 + r] = p;
+        }
+      }
+      l_run = l_run * alpha + sum;
+#pragma unroll
+      for (int hf = 0; hf < HF; ++hf) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc_o[hf][r] *= alpha;
+      }
+#pragma unroll
+      for (int p2 = 0; p2 < NF / 2; ++p2) {
+        const bf16x8 pb = __builtin_convertvector(pf[p2], bf16x8);
+        const int slotb = (kbase + p2 * 32 + g * 8) * 2;
+#pragma unroll
+        for (int hf = 0; hf < HF; ++hf) {
+          const int h = hf * 16 + cl;
+          union {
+            ushortx8 u;
+            bf16x8 h;
+          } va;
+          va.u = *reinterpret_cast<const ushortx8*>(vt_lds + h * vpitch +
+                                                    swz_vt(h, slotb));
+          acc_o[hf] = mfma16x16x32_bf16(va.h, pb, acc_o[hf]);
+        }
+      }
+    }
+
+    float l = l_run;
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    if (qcol < T) {
+      const float inv_l = l > 0.f ? 1.f / l : 0.f;
+      unsigned short* orow = o + (((long)b * T + qcol) * N + n) * H + g * 4;
+#pragma unroll
+      for (int hf = 0; hf < HF; ++hf) {
+        union {
+          ff_bf16x4 h;
+          ushortx4 u;
+        } ov;
+        ov.h = __builtin_convertvector(acc_o[hf] * inv_l, ff_bf16x4);
+        *reinterpret_cast<ushortx4*>(orow + hf * 16) = ov.u;
+      }
+      if (g == 0) {
+        lse[((long)b * N + n) * T + qcol] =
+            l > 0.f ? (m_run + __log2f(l)) * LN2 : NEG_INF;
+      }
     }
   }
 }
@@ -1261,6 +1549,18 @@ static void fa_fwd_dispatch(int H, int ktf, bool seg, Args... args) {
   }
 }
 
+template <class... Args>
+static void fa_fwd_fused_dispatch(bool has_bias, dim3 grid, size_t shmem,
+                                  hipStream_t stream, Args... args) {
+  if (has_bias) {
+    hipLaunchKernelGGL((fa_fwd_fused_kernel<FFW, true>), grid,
+                       dim3(FFW * WAVE_SIZE), shmem, stream, args...);
+  } else {
+    hipLaunchKernelGGL((fa_fwd_fused_kernel<FFW, false>), grid,
+                       dim3(FFW * WAVE_SIZE), shmem, stream, args...);
+  }
+}
+
 template <int H, bool BIAS_GRAD, class... Args>
 static void fa_bwd_launch(dim3 grid, size_t shmem, hipStream_t stream,
                           Args... args) {
@@ -1336,7 +1636,9 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
                                   c10::optional<torch::Tensor> kseg,
                                   int64_t win_l, int64_t win_r,
                                   int64_t bias_clip, double scale,
-                                  int64_t chunk_size, int64_t left_chunks) {
+                                  int64_t chunk_size, int64_t left_chunks,
+                                  const std::string& route) {
+  // Every check comes before the first allocation or launch.
   const long sq = check_strided_btnh(q, "q");
   const long sk = check_strided_btnh(k, "k");
   const long sv = check_strided_btnh(v, "v");
@@ -1346,13 +1648,57 @@ std::vector<torch::Tensor> fa_fwd(torch::Tensor q, torch::Tensor k,
   TORCH_CHECK(N % NKV == 0, "GQA requires N % NKV == 0");
   TORCH_CHECK(k.size(0) == B && k.size(3) == H && v.sizes() == k.sizes(),
               "k/v must be [B,S,NKV,H]");
+  const int nbias = 2 * (int)bias_clip + 1;
+  const bool bias_row_ok =
+      !bias.has_value() ||
+      (bias_clip >= 0 && bias->is_cuda() && bias->is_contiguous() &&
+       bias->scalar_type() == torch::kBFloat16 &&
+       bias->numel() == (long)N * nbias);
+
+  // Route, from shapes only (no device read, so the step still captures
+  // into a graph).
+  bool fused = false;
+  TORCH_CHECK(route == "auto" || route == "tiles" || route == "fused",
+              "fa_fwd: unknown route '", route, "'");
+  const size_t fused_lds =
+      fwd_fused_lds_bytes(std::max(T, 1), bias.has_value(), nbias);
+  if (route != "tiles") {
+    fused = true;
+    const char* why = nullptr;
+    if (H != 64) why = "H != 64";
+    else if (N != NKV) why = "N != NKV";
+    else if (T != S) why = "T != S";
+    else if (S > FWD_FUSED_MAX_S) why = "S above the route's limit";
+    else if (T < 1 || B < 1) why = "empty call";
+    else if (qseg.has_value() || kseg.has_value()) why = "segment ids";
+    else if (chunk_size > 0) why = "chunkwise mask";
+    else if (B > 65535) why = "B above the grid limit";
+    else if (!bias_row_ok) why = "bias is not bf16 [N, 2*bias_clip+1]";
+    else if (fused_lds > fa_lds_limit_bytes()) why = "LDS request too large";
+    if (why) {
+      TORCH_CHECK(route == "auto", "fa_fwd: route '", route,
+                  "' does not support this call: ", why);
+      fused = false;
+    }
+  }
+
   auto o = torch::empty({B, T, N, H}, q.options());
   auto lse = torch::empty({B, N, T}, q.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
-  dim3 grid((T + FQT - 1) / FQT, N, B);
   const int* klp = klen.has_value() ? klen->data_ptr<int>() : nullptr;
   const unsigned short* bp =
       bias.has_value() ? (const unsigned short*)bias->data_ptr() : nullptr;
+  if (fused) {
+    fa_fwd_fused_dispatch(
+        bp != nullptr, dim3(N, B), fused_lds, stream.stream(),
+        (const unsigned short*)q.data_ptr(),
+        (const unsigned short*)k.data_ptr(),
+        (const unsigned short*)v.data_ptr(), klp, bp,
+        (unsigned short*)o.data_ptr(), lse.data_ptr<float>(), T, N,
+        (int)win_l, (int)win_r, (int)bias_clip, (float)scale, sq, sk, sv);
+    return {o, lse};
+  }
+  dim3 grid((T + FQT - 1) / FQT, N, B);
   const int* qsp = qseg.has_value() ? qseg->data_ptr<int>() : nullptr;
   const int* ksp = kseg.has_value() ? kseg->data_ptr<int>() : nullptr;
   // Big KV tiles amortize staging barriers, but waste work on short

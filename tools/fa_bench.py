@@ -2,7 +2,7 @@
 
   python tools/fa_bench.py [--shape conformer|lm] [--iters 50]
                            [--batch B] [--route auto|tiles|fused]
-                           [--ab [--rounds 5] [--ab-iters 3]]
+                           [--ab | --ab-fwd [--rounds 5] [--ab-iters 3]]
 
 Times fwd and bwd separately (bwd via retained graph + backward on a
 fixed grad), prints achieved TFLOP/s against the attention flop count
@@ -11,7 +11,9 @@ fixed grad), prints achieved TFLOP/s against the attention flop count
 --ab times the backward routes interleaved round by round in one process
 (each figure includes everything the route launches: fill, delta and cast
 for 'tiles', the dbias reduce for 'fused') and prints per-route
-median and min over the rounds.
+median and min over the rounds. --ab-fwd does the same for the forward
+routes and adds achieved bytes/s (q, k, v read, o and lse written once) and
+FLOP/s from the counts above.
 """
 
 from __future__ import annotations
@@ -51,6 +53,8 @@ def main():
                   help='fa_bwd route: auto, tiles or fused')
   ap.add_argument('--ab', action='store_true',
                   help='interleaved A/B of the backward routes')
+  ap.add_argument('--ab-fwd', action='store_true',
+                  help='interleaved A/B of the forward routes')
   ap.add_argument('--rounds', type=int, default=5)
   ap.add_argument('--ab-iters', type=int, default=3)
   args = ap.parse_args()
@@ -96,6 +100,33 @@ def main():
 
   print(f'shape={args.shape} B={B} T={T} N={N} H={H} '
         f'bias={"clip" + str(clip) if bias is not None else "none"}')
+  if args.ab_fwd:
+    def fwd(route):
+      return ext.fa_fwd(q, k, v, klen, bias, None, None, -1, -1, clip, scale,
+                        0, 0, route=route)
+
+    routes = ['tiles', 'fused']
+    times = {r: [] for r in routes}
+    for r in routes:  # warm up every route
+      fwd(r)
+    torch.cuda.synchronize()
+    for _ in range(args.rounds):
+      for r in routes:
+        t0 = time.perf_counter()
+        for _ in range(args.ab_iters):
+          fwd(r)
+        torch.cuda.synchronize()
+        times[r].append((time.perf_counter() - t0) / args.ab_iters * 1e3)
+    nbytes = 4 * q.numel() * 2 + lse.numel() * 4
+    print(f'fwd routes, {args.rounds} rounds x {args.ab_iters} iters (ms); '
+          f'{nbytes / 1e6:.1f} MB and {flops_dir / 1e9:.1f} GFLOP per call')
+    for r in routes:
+      med, best = statistics.median(times[r]), min(times[r])
+      print(f'  {r:16s} median {med:8.3f}  min {best:8.3f}  '
+            f'{nbytes / med / 1e9:6.2f} TB/s  '
+            f'{flops_dir / med / 1e9:7.1f} TF/s  rounds '
+            + ' '.join(f'{t:.3f}' for t in times[r]))
+    return
   if args.ab:
     routes = ['tiles', 'fused']
     times = {r: [] for r in routes}
