@@ -166,6 +166,34 @@ class Librispeech960ConformerSCtc(Librispeech960ConformerS):
     return p
 
 
+def _BeamDecode(task_p, num_hyps=8):
+  """Turns on CTC prefix beam search for Decode()."""
+  task_p.decoder.beam_impl = 'auto'
+  task_p.decode_num_hyps = num_hyps
+  return task_p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960WpmConformerLCtcBeam(Librispeech960WpmConformerLCtc):
+  """Librispeech960WpmConformerLCtc decoded with prefix beam search
+  (8 hypotheses, 8 tokens per frame) instead of best-path."""
+
+  def Task(self):
+    p = _BeamDecode(super().Task())
+    p.name = 'librispeech_conformer_l_ctc_beam'
+    return p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960ConformerSCtcBeam(Librispeech960ConformerSCtc):
+  """Librispeech960ConformerSCtc with beam decode: quick tests."""
+
+  def Task(self):
+    p = _BeamDecode(super().Task())
+    p.name = 'librispeech_conformer_s_ctc_beam'
+    return p
+
+
 def _TransducerHead(task_p, joint_dim, rnn_cell_dim):
   """Replaces the attention decoder of `task_p` with a transducer decoder
   (one-layer LSTM prediction network + joint network) of the same

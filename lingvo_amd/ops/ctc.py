@@ -41,12 +41,44 @@ CUDA tensors run ctc_rows_kernel and ctc_viterbi_kernel of ops/hip/ctc.hip
 a batched torch twin of that recursion in the dtype of the input;
 impl='torch' runs the twin on whichever device the inputs are on: the
 composed-ops yardstick for the benchmark.
+
+  beam = ctc_beam_search(logits, logit_lengths, beam_width=8, token_beam=8,
+                         blank_id=0, impl='auto')
+
+is frame-synchronous prefix beam search: the beam_width (W <= 32) most
+probable label sequences, each scored with the log of the sum over all of
+its alignments, as a CtcBeam:
+  topk_ids    [B,W,T] int64  left-packed labels, padded with 0
+  topk_lens   [B,W]   int64
+  topk_scores [B,W]          descending; fp32, or fp64 from fp64 CPU input
+  valid       [B]            1 or 0
+Each frame expands every hypothesis by the blank and by the token_beam
+(C <= 16, clamped to V-1) non-blank tokens with the largest raw logit, the
+lower id winning among equal logits; a repeat of a hypothesis' last token
+that is not among them is impossible in that frame. A hypothesis carries
+(p_b, p_nb), the log-probabilities of its alignments that end in the blank
+and in its last token; extending by the last token continues from p_b
+alone, by any other token from their sum. Candidates that spell the same
+labels are merged by log-sum-exp, and the W candidates with the largest
+p_b (+) p_nb survive; among equal scores a hypothesis that stays comes
+before one that grows, then the better-ranked parent, then the
+better-ranked token. Frames >= T_b are not visited, T_b == 0 gives the
+empty sequence with score 0, and a length outside [0,T] gives valid = 0
+and no hypothesis. Unused slots have length 0, ids 0 and score -1e30. No
+output carries a gradient.
+
+CUDA bf16 / fp32 tensors run ctc_prune_rows_kernel and ctc_beam_kernel of
+ops/hip/ctc_beam.hip (two launches, no host sync, the same bits on every
+run and for bf16 logits as for the same values in fp32). CPU tensors and
+impl='torch' run the textbook search over a dictionary of label tuples in
+the dtype of the input.
 """
 
 from __future__ import annotations
 
 from typing import NamedTuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -55,6 +87,9 @@ from lingvo_amd.ops import _loader
 # Label width the kernels support: one lane per lattice position,
 # 2L+1 <= 1023 lanes of a workgroup.
 MAX_LABEL_LEN = 511
+# Beam search: one lane per candidate, W * (C + 1) <= 544 lanes.
+MAX_BEAM_WIDTH = 32
+MAX_TOKEN_BEAM = 16
 
 _NEG = -1e30
 _NEG_TEST = -1e29
@@ -238,8 +273,7 @@ def _TorchCtc(logits, logit_lengths, labels, label_lengths, blank_id):
   return nll * valid, valid
 
 
-def _CheckArgs(logits, logit_lengths, labels, label_lengths, blank_id,
-               fn='ctc_loss'):
+def _CheckLogits(logits, blank_id, fn):
   if logits.dim() != 3:
     raise ValueError(f'{fn}: logits must be [B,T,V], got '
                      f'{tuple(logits.shape)}')
@@ -255,20 +289,31 @@ def _CheckArgs(logits, logit_lengths, labels, label_lengths, blank_id,
     raise ValueError(f'{fn}: V >= 2')
   if not 0 <= blank_id < v:
     raise ValueError(f'{fn}: blank_id {blank_id} outside [0, {v})')
+
+
+def _CheckLengths(logits, fn, **lengths):
+  for name, x in lengths.items():
+    if x.dim() != 1 or x.shape[0] != logits.shape[0] or \
+        x.is_floating_point() or x.dtype == torch.bool:
+      raise TypeError(f'{fn}: {name} must be an integer tensor [B]')
+    if x.device != logits.device:
+      raise ValueError(f'{fn}: all inputs must be on one device')
+
+
+def _CheckArgs(logits, logit_lengths, labels, label_lengths, blank_id,
+               fn='ctc_loss'):
+  _CheckLogits(logits, blank_id, fn)
+  b = logits.shape[0]
   if labels.dtype != torch.int64 or labels.dim() != 2 or \
       labels.shape[0] != b:
     raise TypeError(f'{fn}: labels must be int64 [B,L]')
   if labels.shape[1] > MAX_LABEL_LEN:
     raise ValueError(f'{fn}: L={labels.shape[1]} is over the supported '
                      f'limit {MAX_LABEL_LEN}')
-  for name, x in (('logit_lengths', logit_lengths),
-                  ('label_lengths', label_lengths)):
-    if x.dim() != 1 or x.shape[0] != b or x.is_floating_point() or \
-        x.dtype == torch.bool:
-      raise TypeError(f'{fn}: {name} must be an integer tensor [B]')
-  for x in (logit_lengths, labels, label_lengths):
-    if x.device != logits.device:
-      raise ValueError(f'{fn}: all inputs must be on one device')
+  _CheckLengths(logits, fn, logit_lengths=logit_lengths,
+                label_lengths=label_lengths)
+  if labels.device != logits.device:
+    raise ValueError(f'{fn}: all inputs must be on one device')
 
 
 def ctc_loss(logits: torch.Tensor, logit_lengths: torch.Tensor,
@@ -403,3 +448,105 @@ def ctc_forced_align(logits: torch.Tensor, logit_lengths: torch.Tensor,
                                        label_lengths, blank_id, True))
   x = logits if logits.dtype == torch.float64 else logits.float()
   return _TwinAlign(x, logit_lengths, labels, label_lengths, blank_id)
+
+
+class CtcBeam(NamedTuple):
+  """What ctc_beam_search returns; see the module docstring."""
+  topk_ids: torch.Tensor     # [B,W,T] int64
+  topk_lens: torch.Tensor    # [B,W] int64
+  topk_scores: torch.Tensor  # [B,W]
+  valid: torch.Tensor        # [B]
+
+
+def _TwinBeam(logits, logit_lengths, w, c, blank_id, on_select=None):
+  """Textbook prefix beam search, one dictionary of candidates per frame
+  keyed by the label tuple, in logits.dtype. Python dictionaries keep
+  insertion order - stays in beam order, then extends by (slot, token
+  rank) - and sorted() is stable, which is the contract's tie rule.
+  on_select(row, scores) sees every frame's live candidate scores, sorted,
+  before the cut to w."""
+  b, t, v = logits.shape
+  c = min(c, v - 1)
+  x = logits.detach().cpu()
+  lp = F.log_softmax(x, dim=-1).numpy()
+  tokens = torch.tensor([i for i in range(v) if i != blank_id])
+  order = torch.sort(x[..., tokens], dim=-1, descending=True, stable=True)
+  cand = tokens[order.indices[..., :c]].numpy()  # ties: the lower id first
+  dt = lp.dtype.type
+  neg = dt(_NEG)
+
+  def lse(p, q):
+    m = max(p, q)
+    if not m > _NEG_TEST:
+      return neg
+    return m + np.log(np.exp(p - m) + np.exp(q - m))
+
+  def add(p, step):
+    return p + step if p > _NEG_TEST else neg
+
+  ids = torch.zeros(b, w, t, dtype=torch.long)
+  lens = torch.zeros(b, w, dtype=torch.long)
+  scores = torch.full((b, w), _NEG, dtype=x.dtype)
+  valid = torch.zeros(b, dtype=x.dtype)
+  for row, tb in enumerate(logit_lengths.cpu().tolist()):
+    if not 0 <= tb <= t:
+      continue
+    valid[row] = 1
+    beam = [((), dt(0), neg)]  # (prefix, p_b, p_nb), best first
+    for frame in range(tb):
+      f_lp, f_tok = lp[row, frame], cand[row, frame].tolist()
+      cands = {}
+      for p, pb, pnb in beam:
+        stay = add(pnb, f_lp[p[-1]]) if p and p[-1] in f_tok else neg
+        cands[p] = [add(lse(pb, pnb), f_lp[blank_id]), stay]
+      for p, pb, pnb in beam:
+        for tok in f_tok:
+          ext = add(pb if p and tok == p[-1] else lse(pb, pnb), f_lp[tok])
+          q = p + (tok,)
+          if q in cands:
+            cands[q][1] = lse(cands[q][1], ext)
+          elif ext > _NEG_TEST:
+            cands[q] = [neg, ext]
+      live = sorted(((lse(pb, pnb), p, pb, pnb)
+                     for p, (pb, pnb) in cands.items()),
+                    key=lambda h: -h[0])
+      if on_select is not None:
+        on_select(row, [h[0] for h in live])
+      beam = [h[1:] for h in live[:w]]
+    for k, (p, pb, pnb) in enumerate(beam):
+      ids[row, k, :len(p)] = torch.tensor(p, dtype=torch.long)
+      lens[row, k] = len(p)
+      scores[row, k] = float(lse(pb, pnb))
+  dev = logits.device
+  return CtcBeam(ids.to(dev), lens.to(dev), scores.to(dev), valid.to(dev))
+
+
+def ctc_beam_search(logits: torch.Tensor, logit_lengths: torch.Tensor,
+                    beam_width: int = 8, token_beam: int = 8,
+                    blank_id: int = 0, impl: str = 'auto') -> CtcBeam:
+  """-> CtcBeam of the beam_width best label sequences; see the module
+  docstring."""
+  fn = 'ctc_beam_search'
+  if impl not in ('auto', 'torch'):
+    raise ValueError(f"{fn}: impl must be 'auto' or 'torch', got {impl!r}")
+  blank_id, beam_width, token_beam = \
+      int(blank_id), int(beam_width), int(token_beam)
+  _CheckLogits(logits, blank_id, fn)
+  _CheckLengths(logits, fn, logit_lengths=logit_lengths)
+  if not 1 <= beam_width <= MAX_BEAM_WIDTH:
+    raise ValueError(f'{fn}: beam_width {beam_width} outside '
+                     f'[1, {MAX_BEAM_WIDTH}]')
+  if not 1 <= token_beam <= MAX_TOKEN_BEAM:
+    raise ValueError(f'{fn}: token_beam {token_beam} outside '
+                     f'[1, {MAX_TOKEN_BEAM}]')
+  logits = logits.detach()
+  logit_lengths = logit_lengths.long().contiguous()
+  if impl == 'auto' and logits.is_cuda:
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+      raise TypeError(f'{fn}: the HIP kernels take bf16 or fp32 logits, got '
+                      f'{logits.dtype}')
+    ext = _loader.get_ext(required=True)
+    return CtcBeam(*ext.ctc_beam_search(logits, logit_lengths, beam_width,
+                                        token_beam, blank_id))
+  x = logits if logits.dtype == torch.float64 else logits.float()
+  return _TwinBeam(x, logit_lengths, beam_width, token_beam, blank_id)

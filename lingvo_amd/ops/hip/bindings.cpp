@@ -229,6 +229,13 @@ std::vector<torch::Tensor> ctc_align(torch::Tensor logits,
                                      torch::Tensor label_lengths,
                                      int64_t blank, bool lds_masks);
 
+// ctc_beam.hip
+std::vector<torch::Tensor> ctc_beam_search(torch::Tensor logits,
+                                           torch::Tensor logit_lengths,
+                                           int64_t beam_width,
+                                           int64_t token_beam,
+                                           int64_t blank);
+
 // xl_attn.hip
 std::vector<torch::Tensor> xl_attn_fwd(torch::Tensor q, torch::Tensor k,
                                        torch::Tensor v, torch::Tensor r,
@@ -438,6 +445,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ctc_align", &ctc_align,
         "CTC forced alignment: frame ids, token spans and log-probs, score, "
         "valid");
+  m.def("ctc_beam_search", &ctc_beam_search,
+        "CTC prefix beam search: topk_ids, topk_lens, topk_scores, valid");
   m.def("xl_attn_fwd", &xl_attn_fwd,
         "Transformer-XL relative attention forward: o, lse");
   m.def("xl_attn_bwd", &xl_attn_bwd,
