@@ -597,6 +597,14 @@ class TransducerDecoder(BaseLayer):
     p.Define('rnnt_impl', 'auto',
              "ops.rnnt.rnnt_loss impl: 'auto' (HIP kernels on GPU, torch "
              "twin on CPU) or 'torch' (fp32 log_softmax + torch ops).")
+    p.Define('beam_token_beam', 8,
+             'BeamSearchDecode: non-blank tokens each hypothesis expands by.')
+    p.Define('beam_impl', 'off',
+             "ops.rnnt.rnnt_beam_search impl for BeamSearchDecode: 'auto' "
+             "(HIP kernels on GPU, the twin on CPU), 'torch' (the twin on "
+             "either device), or 'off': a decoder that was configured "
+             "without beam search stays best-path only and "
+             "BeamSearchDecode raises, as it always did.")
     return p
 
   def __init__(self, params):
@@ -740,9 +748,46 @@ class TransducerDecoder(BaseLayer):
                        enc_paddings: torch.Tensor, num_hyps: int = 8,
                        max_steps: int = 100,
                        length_norm: float = 0.0) -> NestedMap:
-    raise NotImplementedError(
-        'TransducerDecoder.BeamSearchDecode: transducer beam search is not '
-        'built; use GreedyDecode (decode_num_hyps=1)')
+    """Transducer beam search (ops.rnnt.rnnt_beam_search) with num_hyps as
+    the beam width and max_symbols_per_frame labels per frame: topk_ids
+    [B,W,T'*S] left-packed and padded with 0, topk_lens [B,W], topk_scores
+    [B,W] descending, unused slots at -1e30. No host sync under
+    beam_impl='auto'. max_steps is accepted for AsrDecoder's signature and
+    unused; scores are not length-normalised. Needs beam_impl 'auto' or
+    'torch'."""
+    del max_steps
+    p = self.p
+    if p.beam_impl == 'off':
+      raise NotImplementedError(
+          "TransducerDecoder.BeamSearchDecode: transducer beam search is not "
+          "built for this decoder: beam_impl is 'off'; set beam_impl='auto' "
+          "(the ...TransducerBeam configs do), or use GreedyDecode "
+          "(decode_num_hyps=1)")
+    if length_norm != 0.0:
+      raise ValueError(
+          'TransducerDecoder.BeamSearchDecode: length_norm must be 0; length '
+          'normalisation is not built for the transducer')
+    from lingvo_amd.ops import rnnt as rnnt_ops
+    b = enc.shape[0]
+    enc_p = self.enc_proj.FProp(theta.enc_proj, enc.to(self.fprop_dtype))
+
+    def PredFn(tok, states):
+      cells = [NestedMap(c=states[2 * i], m=states[2 * i + 1])
+               for i in range(len(self.rnns))]
+      out, cells = self._PredictionStep(theta, tok, cells)
+      flat = tuple(x for st in cells for x in (st.c, st.m))
+      return self.pred_proj.FProp(theta.pred_proj, out), flat
+
+    init = tuple(x for st in self._InitStates(b * num_hyps, enc.device)
+                 for x in (st.c, st.m))
+    beam = rnnt_ops.rnnt_beam_search(
+        enc_p, py_utils.LengthsFromPaddings(enc_paddings),
+        theta.softmax.linear_w.to(enc_p.dtype), theta.softmax.bias, PredFn,
+        init, beam_width=num_hyps, token_beam=p.beam_token_beam,
+        max_symbols=p.max_symbols_per_frame, blank_id=p.blank_id,
+        impl=p.beam_impl)
+    return NestedMap(topk_ids=beam.topk_ids, topk_lens=beam.topk_lens,
+                     topk_scores=beam.topk_scores)
 
 
 class ShallowFusion:

@@ -167,7 +167,9 @@ class Librispeech960ConformerSCtc(Librispeech960ConformerS):
 
 
 def _BeamDecode(task_p, num_hyps=8):
-  """Turns on CTC prefix beam search for Decode()."""
+  """Turns on beam search for Decode(): CTC prefix beam search on a
+  CtcDecoder, transducer beam search on a TransducerDecoder (both take
+  beam_impl and beam_token_beam)."""
   task_p.decoder.beam_impl = 'auto'
   task_p.decode_num_hyps = num_hyps
   return task_p
@@ -225,6 +227,30 @@ class Librispeech960ConformerSTransducer(Librispeech960ConformerS):
   def Task(self):
     p = _TransducerHead(super().Task(), joint_dim=256, rnn_cell_dim=320)
     p.name = 'librispeech_conformer_s_transducer'
+    return p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960WpmConformerLTransducerBeam(
+    Librispeech960WpmConformerLTransducer):
+  """Librispeech960WpmConformerLTransducer decoded with beam search (8
+  hypotheses, 8 tokens per hypothesis, 3 labels per frame) instead of
+  greedily."""
+
+  def Task(self):
+    p = _BeamDecode(super().Task())
+    p.name = 'librispeech_conformer_l_transducer_beam'
+    return p
+
+
+@registry.RegisterSingleTaskModel
+class Librispeech960ConformerSTransducerBeam(
+    Librispeech960ConformerSTransducer):
+  """Librispeech960ConformerSTransducer with beam decode: quick tests."""
+
+  def Task(self):
+    p = _BeamDecode(super().Task())
+    p.name = 'librispeech_conformer_s_transducer_beam'
     return p
 
 

@@ -312,6 +312,25 @@ torch::Tensor rnnt_bwd(torch::Tensor logits, torch::Tensor logit_lengths,
                        int64_t blank);
 int64_t rnnt_max_label_len();
 
+// rnnt_beam.hip
+std::vector<torch::Tensor> rnnt_beam_init(torch::Tensor enc_lengths,
+                                          int64_t frames, int64_t vocab,
+                                          int64_t beam_width,
+                                          int64_t token_beam,
+                                          int64_t max_symbols);
+void rnnt_beam_joint(torch::Tensor enc_p, int64_t t, torch::Tensor pred_p,
+                     torch::Tensor joint_wt, torch::Tensor joint_b,
+                     std::vector<torch::Tensor> ws, int64_t blank, bool top);
+void rnnt_beam_expand(std::vector<torch::Tensor> ws, torch::Tensor enc_lengths,
+                      int64_t t, int64_t level, int64_t max_symbols,
+                      int64_t frames, int64_t blank);
+void rnnt_beam_close(std::vector<torch::Tensor> ws, torch::Tensor enc_lengths,
+                     int64_t t, int64_t max_symbols, int64_t frames);
+std::vector<torch::Tensor> rnnt_beam_finish(std::vector<torch::Tensor> ws,
+                                            torch::Tensor enc_lengths,
+                                            int64_t max_symbols,
+                                            int64_t frames);
+
 // attn_decode.hip
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor key_cache,
                           torch::Tensor value_cache,
@@ -472,6 +491,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rnnt_bwd", &rnnt_bwd, "Transducer loss backward: dlogits");
   m.def("rnnt_max_label_len", &rnnt_max_label_len,
         "Largest label width U the transducer kernels support");
+  m.def("rnnt_beam_init", &rnnt_beam_init,
+        "Transducer beam search: workspace with the empty beam");
+  m.def("rnnt_beam_joint", &rnnt_beam_joint,
+        "Transducer beam search level: fused joint + prune partials");
+  m.def("rnnt_beam_expand", &rnnt_beam_expand,
+        "Transducer beam search level: pool entries, next level, parent/token");
+  m.def("rnnt_beam_close", &rnnt_beam_close,
+        "Transducer beam search frame: merge the pool, next beam, source index");
+  m.def("rnnt_beam_finish", &rnnt_beam_finish,
+        "Transducer beam search: topk_ids, topk_lens, topk_scores, valid");
   m.def("attn_decode", &attn_decode,
         "KV-cache attention (ExtendStep/StreamStep): split-K decode kernel "
         "+ combine",

@@ -32,10 +32,70 @@ in the input's dtype and float32. impl='torch' on either device is log_softmax i
 inputs) followed by the same per-diagonal recursion in torch ops,
 differentiated by autograd: the route the kernels are timed against. It
 materialises the fp32 [B,T,U+1,V] log-probabilities.
+
+  beam = rnnt_beam_search(enc_p, enc_lengths, joint_w, joint_b, pred_fn,
+                          init_states, beam_width=8, token_beam=8,
+                          max_symbols=3, blank_id=0, impl='auto')
+
+is time-synchronous transducer beam search with at most S = max_symbols
+labels per frame and prefix merging at the end of each frame. enc_p
+[B,T,J] is the projected encoder output, joint_w [J,V] and joint_b [V] the
+softmax layer of the joint, joint(e, p) = tanh(e + p) @ joint_w + joint_b.
+pred_fn(tok [R] long, states) -> (pred_p [R,J], new_states) is one
+prediction-network step plus its projection over R = B*W rows; states is
+a tuple of tensors with leading dimension R and init_states the one to
+start from. The search, with W = beam_width and C = token_beam:
+
+  beam: W slots (label sequence, score, prediction-network state).
+        Start: slot 0 = empty sequence, score 0; the others dead (-1e30).
+  for t in 0 .. T_b-1:
+    A = beam; pool = []
+    for s in 0 .. S:                     # s labels emitted so far in this frame
+      lp = log_softmax(joint(enc_p[b,t], pred_p[A]))         # per live slot of A
+      pool[s*W + i] = (A_i.seq, A_i.score + lp[i, blank])    # every live i
+      if s == S: break
+      candidates (i, r), r < C: A_i.seq + tok_r(i), A_i.score + lp[i, tok_r(i)]
+          tok_r(i) = the non-blank token with the r-th largest raw logit in
+          row i (equal logits: the lower id first); C is clamped to V-1
+      A = the W best candidates (larger score; then lower i; then lower r)
+      advance the prediction network by one step for the new A
+    merge pool entries with equal label sequences: logaddexp into the entry
+        with the lowest pool index; the others die
+    beam = the W best live pool entries (larger score, then lower pool index)
+  frames t >= T_b are not visited.
+
+Two entries of one level never spell the same labels (they would share
+their ancestor and their token), so duplicates arise only across levels,
+in the pool. pred_fn is called once with the blank to start the history
+and then once per level for all R rows; dead rows get the blank and their
+outputs are ignored. The result is the final beam, descending, as an
+RnntBeam:
+  topk_ids    [B,W,T*S] int64  left-packed labels, padded with 0
+  topk_lens   [B,W]     int64
+  topk_scores [B,W]            fp32, or fp64 from fp64 CPU input
+  valid       [B]              1 or 0
+Unused slots have length 0, ids 0 and score -1e30. T_b == 0 gives the
+empty hypothesis with score 0; a length outside [0,T] gives valid = 0 and
+no hypothesis. No output carries a gradient.
+
+impl='auto' on CUDA runs the kernels of ops/hip/rnnt_beam.hip: per level a
+fused joint + prune launch (the [R,V] logits never reach memory) and an
+expand launch, per frame a close launch, at the end a backtrace; the
+state gathers and pred_fn stay in torch. No host sync; all T frames run
+with static shapes and utterances past their length are frozen by the
+kernels. Limits: bf16 enc_p, pred_p and joint_w (joint_b bf16 or fp32),
+W <= 32, C <= 16, S <= 4, J % 32 == 0 and J <= 1024, any V >= 2; other
+CUDA inputs are refused. CPU tensors and impl='torch' run _TwinRnntBeam,
+the definition above over Python lists of label tuples, in the dtype of
+the input (fp32 for bf16 input, with tanh(.) rounded to bf16 as the
+kernels' MFMA operand is).
 """
 
 from __future__ import annotations
 
+from typing import NamedTuple
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -44,6 +104,12 @@ from lingvo_amd.ops import _loader
 # Label width the kernels support: one lane per u, U+1 <= 1024 lanes of a
 # workgroup.
 MAX_LABEL_LEN = 1023
+# Beam search: one lane per candidate (W*C <= 512), (S+1)*W pool entries in
+# LDS, and a resident 32 x J bf16 tile of at most 64 KB.
+MAX_BEAM_WIDTH = 32
+MAX_TOKEN_BEAM = 16
+MAX_SYMBOLS = 4
+MAX_JOINT_DIM = 1024
 
 _NEG = -1e30
 _NEG_TEST = -1e29
@@ -332,3 +398,227 @@ def rnnt_loss(logits: torch.Tensor, logit_lengths: torch.Tensor,
                     f'got {logits.dtype}')
   return _RnntLossFn.apply(logits, logit_lengths, labels, label_lengths,
                            blank_id)
+
+
+class RnntBeam(NamedTuple):
+  """What rnnt_beam_search returns; see the module docstring."""
+  topk_ids: torch.Tensor     # [B,W,T*S] int64
+  topk_lens: torch.Tensor    # [B,W] int64
+  topk_scores: torch.Tensor  # [B,W]
+  valid: torch.Tensor        # [B]
+
+
+def _Rows(states, index):
+  return tuple(x.index_select(0, index) for x in states)
+
+
+def _Pool(levels, b, w):
+  """S+1 tensors [B*W,...] -> [B*(S+1)*W,...], entry b*(S+1)*W + s*W + i."""
+  return torch.stack([x.reshape(b, w, *x.shape[1:]) for x in levels],
+                     dim=1).flatten(0, 2)
+
+
+def _TwinRnntBeam(enc_p, enc_lengths, joint_w, joint_b, pred_fn, init_states,
+                  w, c, s_max, blank_id, operand_dtype=None, on_select=None):
+  """The search of the module docstring, literally: Python lists of (label
+  tuple, score) per utterance, scores in enc_p.dtype (fp32 or fp64), the
+  prediction network batched over all B*W rows as the kernels' host loop
+  runs it. operand_dtype rounds tanh(enc_p + pred_p) to that dtype before
+  the product with joint_w, which stays wide: the operands the MFMA sees.
+  on_select('select', b, scores, w) sees every selection's candidate
+  scores, sorted, before the cut to w; on_select('tokens', row, logits, c)
+  every live row's non-blank raw logits, sorted, before the cut to c."""
+  b, t, _ = enc_p.shape
+  v = joint_w.shape[1]
+  c = min(c, v - 1)
+  dev, dt = enc_p.device, enc_p.dtype
+  npdt = np.float64 if dt == torch.float64 else np.float32
+  jw, jb = joint_w.to(dt), joint_b.to(dt)
+  tokens = torch.tensor([i for i in range(v) if i != blank_id], device=dev)
+  r, p = b * w, (s_max + 1) * w
+  lens = enc_lengths.cpu().tolist()
+  ok = [0 <= n <= t for n in lens]
+
+  def lse(x, y):
+    m = max(x, y)
+    return m + np.log(np.exp(x - m) + np.exp(y - m))
+
+  def rows(values):
+    return torch.tensor(values, dtype=torch.long, device=dev)
+
+  beams = [[((), npdt(0))] if good else [] for good in ok]
+  pred_p, states = pred_fn(rows([blank_id] * r), tuple(init_states))
+  for f in range(t):
+    active = [ok[i] and f < lens[i] for i in range(b)]
+    if not any(active):
+      break
+    cur = [list(beams[i]) if active[i] else [] for i in range(b)]
+    pool = [[] for _ in range(b)]
+    lv_pred, lv_states = [], []
+    for lvl in range(s_max + 1):
+      lv_pred.append(pred_p)
+      lv_states.append(states)
+      x = torch.tanh(enc_p[:, f].repeat_interleave(w, dim=0) + pred_p.to(dt))
+      if operand_dtype is not None:
+        x = x.to(operand_dtype).to(dt)
+      logits = x @ jw + jb
+      lp = (logits - torch.logsumexp(logits, -1, keepdim=True)).cpu().numpy()
+      order = torch.sort(logits[:, tokens], dim=-1, descending=True,
+                         stable=True)  # ties: the lower id first
+      top = tokens[order.indices[:, :c]].cpu().tolist()
+      top_vals = order.values.cpu().numpy()
+      parent = [i * w for i in range(b) for _ in range(w)]
+      tok = [blank_id] * r
+      for i in range(b):
+        for k, (seq, score) in enumerate(cur[i]):
+          pool[i].append((lvl * w + k, seq, score + lp[i * w + k, blank_id]))
+        if lvl == s_max or not cur[i]:
+          continue
+        cands = []
+        for k, (seq, score) in enumerate(cur[i]):
+          if on_select is not None:
+            on_select('tokens', i * w + k, top_vals[i * w + k].tolist(), c)
+          cands += [(score + lp[i * w + k, tk], k, tk) for tk in top[i * w + k]]
+        cands.sort(key=lambda h: -h[0])  # stable: then slot, then token rank
+        if on_select is not None:
+          on_select('select', i, [h[0] for h in cands], w)
+        new = []
+        for slot, (score, k, tk) in enumerate(cands[:w]):
+          new.append((cur[i][k][0] + (tk,), score))
+          parent[i * w + slot], tok[i * w + slot] = i * w + k, tk
+        cur[i] = new
+      if lvl < s_max:
+        pred_p, states = pred_fn(rows(tok), _Rows(states, rows(parent)))
+    # Level 0 of the pool is the beam itself: where a frozen row stays.
+    src = [i * p + k for i in range(b) for k in range(w)]
+    for i in range(b):
+      if not active[i]:
+        continue
+      merged = {}  # insertion order is pool order
+      for idx, seq, score in pool[i]:
+        if seq in merged:
+          merged[seq][1] = lse(merged[seq][1], score)
+        else:
+          merged[seq] = [idx, score]
+      live = sorted(((score, idx, seq) for seq, (idx, score) in merged.items()),
+                    key=lambda h: -h[0])
+      if on_select is not None:
+        on_select('select', i, [h[0] for h in live], w)
+      beams[i] = [(seq, score) for score, _, seq in live[:w]]
+      for k in range(w):
+        src[i * w + k] = i * p + (live[k][1] if k < len(live) else 0)
+    src = rows(src)
+    pred_p = _Pool(lv_pred, b, w).index_select(0, src)
+    states = tuple(
+        _Pool([st[k] for st in lv_states], b, w).index_select(0, src)
+        for k in range(len(states)))
+
+  ids = torch.zeros(b, w, t * s_max, dtype=torch.long)
+  out_lens = torch.zeros(b, w, dtype=torch.long)
+  scores = torch.full((b, w), _NEG, dtype=dt)
+  for i, beam in enumerate(beams):
+    for k, (seq, score) in enumerate(beam):
+      ids[i, k, :len(seq)] = torch.tensor(seq, dtype=torch.long)
+      out_lens[i, k] = len(seq)
+      scores[i, k] = float(score)
+  valid = torch.tensor([float(good) for good in ok], dtype=dt)
+  return RnntBeam(ids.to(dev), out_lens.to(dev), scores.to(dev),
+                  valid.to(dev))
+
+
+def _HipRnntBeam(enc_p, enc_lengths, joint_w, joint_b, pred_fn, init_states,
+                 w, c, s_max, blank_id):
+  """The host loop around the kernels of ops/hip/rnnt_beam.hip: launches,
+  index_select and pred_fn, all on the current stream."""
+  fn = 'rnnt_beam_search'
+  ext = _loader.get_ext(required=True)
+  b, t, j = enc_p.shape
+  v = joint_w.shape[1]
+  wt = joint_w.t().contiguous()  # [V,J]: K-contiguous for the B fragments
+  bias = joint_b.float().contiguous()
+  ws = ext.rnnt_beam_init(enc_lengths, t, v, w, min(c, v - 1), s_max)
+  parent, tok, src = ws[7], ws[8], ws[9]
+  start = torch.full((b * w,), blank_id, dtype=torch.long, device=enc_p.device)
+  pred_p, states = pred_fn(start, tuple(init_states))
+  for f in range(t):
+    lv_pred, lv_states = [], []
+    for lvl in range(s_max + 1):
+      if pred_p.dtype != torch.bfloat16 or pred_p.shape != (b * w, j):
+        raise TypeError(f'{fn}: the HIP kernels take bf16 pred_p [B*W,J] from '
+                        f'pred_fn, got {pred_p.dtype} {tuple(pred_p.shape)}')
+      pred_p = pred_p.contiguous()
+      lv_pred.append(pred_p)
+      lv_states.append(states)
+      ext.rnnt_beam_joint(enc_p, f, pred_p, wt, bias, ws, blank_id,
+                          lvl < s_max)
+      ext.rnnt_beam_expand(ws, enc_lengths, f, lvl, s_max, t, blank_id)
+      if lvl < s_max:
+        pred_p, states = pred_fn(tok, _Rows(states, parent))
+        states = tuple(states)
+    ext.rnnt_beam_close(ws, enc_lengths, f, s_max, t)
+    pred_p = _Pool(lv_pred, b, w).index_select(0, src)
+    states = tuple(
+        _Pool([st[k] for st in lv_states], b, w).index_select(0, src)
+        for k in range(len(states)))
+  return RnntBeam(*ext.rnnt_beam_finish(ws, enc_lengths, s_max, t))
+
+
+def rnnt_beam_search(enc_p: torch.Tensor, enc_lengths: torch.Tensor,
+                     joint_w: torch.Tensor, joint_b: torch.Tensor, pred_fn,
+                     init_states, beam_width: int = 8, token_beam: int = 8,
+                     max_symbols: int = 3, blank_id: int = 0,
+                     impl: str = 'auto') -> RnntBeam:
+  """-> RnntBeam of the beam_width best label sequences; see the module
+  docstring."""
+  fn = 'rnnt_beam_search'
+  if impl not in ('auto', 'torch'):
+    raise ValueError(f"{fn}: impl must be 'auto' or 'torch', got {impl!r}")
+  w, c, s_max, blank_id = \
+      int(beam_width), int(token_beam), int(max_symbols), int(blank_id)
+  if enc_p.dim() != 3 or not enc_p.is_floating_point():
+    raise ValueError(f'{fn}: enc_p must be floating point [B,T,J], got '
+                     f'{enc_p.dtype} {tuple(enc_p.shape)}')
+  b, t, j = enc_p.shape
+  if b < 1 or t < 1:
+    raise ValueError(f'{fn}: B >= 1 and T >= 1')
+  if joint_w.dim() != 2 or joint_w.shape[0] != j or joint_w.shape[1] < 2:
+    raise ValueError(f'{fn}: joint_w must be [J={j},V>=2], got '
+                     f'{tuple(joint_w.shape)}')
+  v = joint_w.shape[1]
+  if joint_b.shape != (v,):
+    raise ValueError(f'{fn}: joint_b must be [V={v}], got '
+                     f'{tuple(joint_b.shape)}')
+  if not 0 <= blank_id < v:
+    raise ValueError(f'{fn}: blank_id {blank_id} outside [0, {v})')
+  if enc_lengths.dim() != 1 or enc_lengths.shape[0] != b or \
+      enc_lengths.is_floating_point() or enc_lengths.dtype == torch.bool:
+    raise TypeError(f'{fn}: enc_lengths must be an integer tensor [B]')
+  for x in (enc_lengths, joint_w, joint_b):
+    if x.device != enc_p.device:
+      raise ValueError(f'{fn}: all inputs must be on one device')
+  for name, got, top in (('beam_width', w, MAX_BEAM_WIDTH),
+                         ('token_beam', c, MAX_TOKEN_BEAM),
+                         ('max_symbols', s_max, MAX_SYMBOLS)):
+    if not 1 <= got <= top:
+      raise ValueError(f'{fn}: {name} {got} outside [1, {top}]')
+  enc_lengths = enc_lengths.long().contiguous()
+  with torch.no_grad():
+    enc_p, joint_w, joint_b = \
+        enc_p.detach(), joint_w.detach(), joint_b.detach()
+    if impl == 'auto' and enc_p.is_cuda:
+      if enc_p.dtype != torch.bfloat16 or joint_w.dtype != torch.bfloat16:
+        raise TypeError(f'{fn}: the HIP kernels take bf16 enc_p and joint_w, '
+                        f'got {enc_p.dtype} and {joint_w.dtype}')
+      if joint_b.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f'{fn}: the HIP kernels take bf16 or fp32 joint_b, '
+                        f'got {joint_b.dtype}')
+      if j % 32 != 0 or j > MAX_JOINT_DIM:
+        raise ValueError(f'{fn}: the HIP kernels need J % 32 == 0 and J <= '
+                         f'{MAX_JOINT_DIM}, got J={j}')
+      return _HipRnntBeam(enc_p.contiguous(), enc_lengths, joint_w, joint_b,
+                          pred_fn, init_states, w, c, s_max, blank_id)
+    wide = enc_p.dtype in (torch.float32, torch.float64)
+    x = enc_p if wide else enc_p.float()
+    return _TwinRnntBeam(x, enc_lengths, joint_w, joint_b, pred_fn,
+                         init_states, w, c, s_max, blank_id,
+                         operand_dtype=None if wide else enc_p.dtype)
