@@ -21,8 +21,9 @@
 //    'fused' (fa_bwd_fused_kernel): self-attention with N == NKV, H == 64,
 //    T == S <= 384, no segment ids or chunkwise mask. Grid (N, B), one
 //    workgroup of 8 waves per head; strips of 16 keys live across the
-//    waves with K/V fragments and dK/dV accumulators in registers; the
-//    32-row q-tiles are walked once, loads for the next tile in flight;
+//    waves with K/V fragments and dK/dV accumulators in registers; P and
+//    dS go to the dV and dK MFMAs from registers (see the kernel's header);
+//    the 32-row q-tiles are walked once, loads for the next tile in flight;
 //    delta = rowsum(dO*O) is reduced while dO is staged; dQ is contracted
 //    over all keys from a [32][S_pad] dS tile in LDS, rounded once and
 //    stored as bf16; the bias gradient leaves as one fp32 row per
@@ -1070,9 +1071,21 @@ __global__ void fa_dq_cast(const float* __restrict__ dq_acc,
 // with N == NKV and T == S <= FUSED_MAX_S.
 //
 // Keys across waves: strip s (16 keys) belongs to wave s % NWF, which keeps
-// the strip's K/V A-fragments and dK/dV accumulators in registers for the
-// whole kernel. The q-tiles are walked once. Per tile every wave writes its
-// dS strips into one [FQTB][S_pad] LDS tile; after a barrier dQ^T = K^T dS^T
+// the strip's K/V fragments and dK^T/dV^T accumulators in registers for the
+// whole kernel. The q-tiles are walked once.
+//
+// S = Q K^T and dP = dO V^T: in the MFMA C layout a lane holds one key (its
+// column cl) and queries g*4 + r of each 16-query fragment. The two query
+// fragments of a 32-row tile are the 8 k-slots of one contraction step, slot
+// g*8 + hs*4 + r <-> query hs*16 + g*4 + r, so P and dS, converted in pairs,
+// are the B operands of dV^T = dO^T P and dK^T = Q^T dS straight from
+// registers; Q^T and dO^T are staged in that slot order. lse and delta are
+// one 16-byte broadcast read per fragment. Logits are base-2 (scale, the
+// bias row and the staged lse carry log2 e). A lane ends with 4 consecutive
+// h of one key: 8-byte dK/dV stores.
+//
+// Per tile every wave also writes its dS strips into one [FQTB][S_pad] LDS
+// tile (that contraction crosses waves); after a barrier dQ^T = K^T dS^T
 // is computed over the whole key range (K^T resident in LDS), rounded once
 // and stored as bf16 straight into dq. delta = rowsum(dO * O) is reduced
 // while the dO tile is staged. Global loads for tile i+1 are issued into
@@ -1089,18 +1102,41 @@ constexpr int NWF = 8;                         // waves
 constexpr int SPW = 3;                         // key strips per wave
 constexpr int FUSED_MAX_S = NWF * SPW * 16;
 
+// Row pitch in bytes of the fused backward's dS tile.
+constexpr int FUSED_DS_PITCH = FUSED_MAX_S * 2 + 16;
+
 // Dynamic LDS bytes of fa_bwd_fused_kernel (H == 64).
 static size_t fused_lds_bytes(bool has_bias, bool bias_grad, int nbias) {
   constexpr int H = 64;
   constexpr int SP = FUSED_MAX_S;
   return (size_t)FQTB * H * 2 * 2          // q_lds + do_lds
-         + (size_t)H * 128 * 2             // qt_lds + dot_lds (128B pitch)
+         + (size_t)H * FQTB * 2 * 2        // qt_lds + dot_lds
          + (size_t)H * SP * 2              // kt_lds
-         + (size_t)FQTB * SP * 2           // ds_lds
-         + (size_t)NWF * 16 * 128          // a_lds (128B pitch)
+         + (size_t)FQTB * FUSED_DS_PITCH   // ds_lds
          + 2 * FQTB * sizeof(float)        // lse_s + delta_s
-         + (has_bias ? nbias * sizeof(float) : 0)
+         + (has_bias ? nbias : 1) * sizeof(float)
          + (bias_grad ? (2 * SP + FQTB) * sizeof(float) : 0);
+}
+
+// Q^T and dO^T tiles: row h holds the tile's 32 queries in the k-slot order
+// of the MFMA that contracts over them, slot g*8 + hs*4 + r <-> query
+// hs*16 + g*4 + r, so an A fragment is one 16-byte read and the rows need
+// no padding (64 bytes). The four 16-byte granules of a row are exchanged
+// by h/8: a wave's fragment read still covers 1 KB exactly once, and the
+// staging writes of one query row spread over four bank groups.
+__device__ __forceinline__ int qslot_byte(int h, int q) {
+  const int slot = ((q >> 2) & 3) * 8 + (q >> 4) * 4 + (q & 3);
+  return (slot * 2) ^ (((h >> 3) & 3) << 4);
+}
+
+// One 16-byte fragment read at an LDS address.
+__device__ __forceinline__ bf16x8 frag_at(const char* p) {
+  union {
+    ushortx8 u;
+    bf16x8 h;
+  } cv;
+  cv.u = *reinterpret_cast<const ushortx8*>(p);
+  return cv.h;
 }
 
 template <int H, bool BIAS_GRAD>
@@ -1122,13 +1158,18 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
   constexpr int KH = H / 32;
   constexpr int HF = H / 16;
   constexpr int NQ = FQTB / 16;
-  constexpr int TP = 128;        // pitch of the [..][FQTB] tiles (swizzle span)
-  constexpr int DSP = SP * 2;    // pitch of the [..][SP] tiles
+  constexpr int TP = FQTB * 2;   // pitch of the [..][FQTB] tiles
+  constexpr int DSP = SP * 2;    // pitch of the K^T tile
+  // Pitch of the dS tile: rows skewed by 16 bytes instead of swizzled, so a
+  // lane's dS writes are constant offsets from one address.
+  constexpr int DSQ = FUSED_DS_PITCH;
   constexpr int NDACC = 2 * SP + FQTB;
   constexpr int STG = FQTB * (ROWB / 16);       // staging threads (16B each)
+  constexpr float LOG2E = 1.4426950408889634f;
   static_assert(SP % 64 == 0, "[..][SP] rows must span whole swizzle blocks");
   static_assert((NWF * SPW) % 2 == 0, "dQ contracts over pairs of strips");
-  static_assert(FQTB <= 64 && FQTB % 16 == 0 && STG <= NT, "q-tile shape");
+  // A q-tile is one 32-deep contraction step of the dV and dK MFMAs.
+  static_assert(FQTB == 32 && STG <= NT, "q-tile shape");
   // dQ^T output tiles (FQTB/16 x H/16) over the waves; a wave's tiles share
   // their dS B-fragment.
   constexpr int NTILE = NQ * HF;
@@ -1139,16 +1180,16 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
   extern __shared__ char smem[];
   char* q_lds = smem;                        // [FQTB][H] swz
   char* do_lds = q_lds + FQTB * ROWB;         // [FQTB][H] swz
-  char* qt_lds = do_lds + FQTB * ROWB;        // [H][FQTB] swz, pitch TP
-  char* dot_lds = qt_lds + H * TP;           // [H][FQTB] swz, pitch TP
+  char* qt_lds = do_lds + FQTB * ROWB;        // [H][slot], qslot_byte
+  char* dot_lds = qt_lds + H * TP;           // [H][slot], qslot_byte
   char* kt_lds = dot_lds + H * TP;           // [H][SP] swz
-  char* ds_lds = kt_lds + H * DSP;           // [FQTB][SP] swz
-  char* a_lds = ds_lds + FQTB * DSP;          // [NWF][16][FQTB] swz, pitch TP
-  float* lse_s = (float*)(a_lds + NWF * 16 * TP);       // [FQTB]
+  char* ds_lds = kt_lds + H * DSP;           // [FQTB][SP], pitch DSQ
+  float* lse_s = (float*)(ds_lds + FQTB * DSQ);          // [FQTB], * log2 e
   float* delta_s = lse_s + FQTB;                         // [FQTB]
-  float* bias_s = delta_s + FQTB;                        // [nbias] if bias
+  float* bias_s = delta_s + FQTB;   // [nbias] * log2 e; one zero without bias
   // Unclipped per-diagonal sums, slot = (q - key) + SP - 1.
-  float* dacc = bias_s + (bias ? nbias : 0);            // [NDACC] if BIAS_GRAD
+  float* dacc = bias_s + (bias ? nbias : 1);            // [NDACC] if BIAS_GRAD
+  const int bias_top = bias ? nbias - 1 : 0;
 
   const int n = blockIdx.x;
   const int b = blockIdx.y;
@@ -1166,6 +1207,9 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
   // far from overflow).
   const int wl = win_l < 0 ? 0x3fffffff : win_l;
   const int wr = win_r < 0 ? 0x3fffffff : win_r;
+  // Logits are kept in the base-2 domain: scale, the bias row and lse carry
+  // log2 e, and p is one v_exp_f32 of a difference.
+  const float sc2 = scale * LOG2E;
 
   // Staging role of this thread: 16 bytes of one q/dO/O row; the last FQTB
   // threads carry lse.
@@ -1173,6 +1217,17 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
   const int sc = tid % (ROWB / 16);
   const bool stager = tid < STG;
   const int lrow = tid - (NT - FQTB);
+  // Byte of query srow in the rows h = sc*8 .. sc*8 + 7 of Q^T and dO^T.
+  const int sslot = qslot_byte(sc * 8, srow & (FQTB - 1));
+  // Per-lane LDS offsets of the strip phase; everything else is a constant.
+  // fq: fragment (row cl, h = kk*32 + g*8) of a 16-row block of q or dO.
+  // ft: fragment (row cl, slots g*8 ..) of an even / odd 16-row block of Q^T
+  // or dO^T. dsw: dS tile entry (row g*4, key cl of the wave's first strip).
+  const int fq[KH] = {cl * ROWB + swz(cl, g * 16),
+                      cl * ROWB + swz(cl, 64 + g * 16)};
+  const int ft[2] = {cl * TP + ((g ^ (cl >> 3)) << 4),
+                     cl * TP + ((g ^ (2 + (cl >> 3))) << 4)};
+  char* dsw = ds_lds + g * 4 * DSQ + (wid * 16 + cl) * 2;
   ushortx8 pq, pdo, po;
   float plse = 0.f;
 #pragma unroll
@@ -1195,7 +1250,7 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
 
   // One-time LDS setup: dS tile zeroed (columns of the odd padding strip
   // are read by dQ but never written), bias row, diagonal sums, K^T.
-  for (int i = tid; i < FQTB * DSP / 16; i += NT) {
+  for (int i = tid; i < FQTB * DSQ / 16; i += NT) {
     ushortx8 z;
 #pragma unroll
     for (int j = 0; j < 8; ++j) z[j] = 0;
@@ -1203,7 +1258,9 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
   }
   if (bias) {
     for (int i = tid; i < nbias; i += NT)
-      bias_s[i] = bf16_bits_to_float(bias[(long)n * nbias + i]);
+      bias_s[i] = bf16_bits_to_float(bias[(long)n * nbias + i]) * LOG2E;
+  } else if (tid == 0) {
+    bias_s[0] = 0.f;
   }
   if (BIAS_GRAD) {
     for (int i = tid; i < NDACC; i += NT) dacc[i] = 0.f;
@@ -1221,7 +1278,9 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
     }
   }
 
-  // K, V fragments (A layout) and accumulators of this wave's strips.
+  // K, V fragments and accumulators of this wave's strips. A fragment holds
+  // key cl, h = kk*32 + g*8 ..: the B operand of S = Q K^T and dP = dO V^T.
+  // dK^T and dV^T accumulate as [h][key].
   bf16x8 kfrag[SPW][KH], vfrag[SPW][KH];
   f32x4 acc_dk[SPW][HF], acc_dv[SPW][HF];
 #pragma unroll
@@ -1248,7 +1307,6 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
     }
   }
 
-  char* aw = a_lds + wid * 16 * TP;
   for (int qt = 0; qt < nqt; ++qt) {
     const int qb = qt * FQTB;
     // No barrier here: q/dO/lse/delta were last read before the barrier
@@ -1269,11 +1327,9 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
                                    swz(srow, sc * 16)) = pdo;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const int h = sc * 8 + j;
-        *reinterpret_cast<unsigned short*>(qt_lds + h * TP +
-                                           swz(h, srow * 2)) = pq[j];
-        *reinterpret_cast<unsigned short*>(dot_lds + h * TP +
-                                           swz(h, srow * 2)) = pdo[j];
+        const int off = (sc * 8 + j) * TP + sslot;
+        *reinterpret_cast<unsigned short*>(qt_lds + off) = pq[j];
+        *reinterpret_cast<unsigned short*>(dot_lds + off) = pdo[j];
       }
       // delta: the row's ROWB/16 = 8 threads are neighbouring lanes.
 #pragma unroll
@@ -1281,111 +1337,86 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
         part += __shfl_xor(part, off);
       if (sc == 0) delta_s[srow] = part;
     }
-    if (lrow >= 0) lse_s[lrow] = qb + lrow < T ? plse : NEG_INF;
+    // Rows past T and rows without a visible key get a large positive lse:
+    // every p of the row is exp2 of a hugely negative number, an exact 0.
+    if (lrow >= 0)
+      lse_s[lrow] = (qb + lrow < T) & (plse > NEG_INF * 0.5f) ? plse * LOG2E
+                                                             : -NEG_INF;
     __syncthreads();
     if (qt + 1 < nqt) prefetch(qb + FQTB);
 
+    if (wid < nact) {   // wave-uniform: the wave has a strip with a key
+      // The tile's operands are read again for each strip: held across the
+      // wave's three strips (64 registers, or 32 for q and dO alone) they
+      // push the accumulators into scratch (docs/KERNEL_NOTES.md).
+      const int qbase = qb + g * 4;   // query of tile row c = 0 of this lane
+
 #pragma unroll
-    for (int si = 0; si < SPW; ++si) {
-      const int strip = wid + si * NWF;
-      if (strip >= nact) continue;   // wave-uniform
-      const int k0 = strip * 16;
-      // S^T strip: rows = 16 keys, cols = FQTB queries.
-      float pt[NQ][4];   // P^T
-      float dlg[NQ][4];  // dLogits
+      for (int si = 0; si < SPW; ++si) {
+        const int strip = wid + si * NWF;
+        if (strip >= nact) continue;   // wave-uniform
+        // A lane holds key cl of the strip and tile rows c = nf*16 + r
+        // (queries qbase + c). Visible rows of the key: [lo, lo + span).
+        const int key = strip * 16 + cl;
+        const int lo = max(key - wr, 0) - qbase;
+        const int hi = min(key + wl, SP + FQTB) - qbase;
+        const int span = key < klen ? max(hi - lo + 1, 0) : 0;
+        const int i0 = qbase - key + bias_clip;   // bias row entry of c = 0
+        ff_floatx8 pf, dsf;   // P and dS in slot order j = nf*4 + r
 #pragma unroll
-      for (int nf = 0; nf < NQ; ++nf) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int nf = 0; nf < NQ; ++nf) {
+          f32x4 acc = {0.f, 0.f, 0.f, 0.f};    // S = Q K^T
+          f32x4 accd = {0.f, 0.f, 0.f, 0.f};   // dP = dO V^T
 #pragma unroll
-        for (int kk = 0; kk < KH; ++kk) {
-          bf16x8 bq =
-              lds_frag(q_lds, nf * 16 + cl, ROWB, (kk * 32 + g * 8) * 2);
-          acc = mfma16x16x32_bf16(kfrag[si][kk], bq, acc);
-        }
-        const int qcol = qb + nf * 16 + cl;
-        const float l = lse_s[nf * 16 + cl];
-        const bool lok = (qcol < T) & (l > NEG_INF * 0.5f);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = k0 + g * 4 + r;
-          float val = acc[r] * scale;
-          if (bias) {
-            int d = qcol - key;
-            d = d < -bias_clip ? -bias_clip : (d > bias_clip ? bias_clip : d);
-            val += bias_s[d + bias_clip];
+          for (int kk = 0; kk < KH; ++kk) {
+            acc = mfma16x16x32_bf16(
+                frag_at(q_lds + nf * 16 * ROWB + fq[kk]), kfrag[si][kk], acc);
+            accd = mfma16x16x32_bf16(
+                frag_at(do_lds + nf * 16 * ROWB + fq[kk]), vfrag[si][kk],
+                accd);
           }
-          // visible() without its early returns: one select per element
-          // instead of a branch tree.
-          const bool vis = (key < klen) & (key >= qcol - wl) &
-                           (key <= qcol + wr) & lok;
-          pt[nf][r] = vis ? __expf(val - l) : 0.f;
+          const f32x4 l2 =
+              *reinterpret_cast<const f32x4*>(lse_s + nf * 16 + g * 4);
+          const f32x4 dl =
+              *reinterpret_cast<const f32x4*>(delta_s + nf * 16 + g * 4);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = nf * 16 + r;
+            // Without a bias the row is one zero: no per-logit branch.
+            const int i = min(max(i0 + c, 0), bias_top);
+            float val = fmaf(acc[r], sc2, bias_s[i]);
+            val = (unsigned)(c - lo) < (unsigned)span ? val : NEG_INF;
+            const float p = __builtin_amdgcn_exp2f(val - l2[r]);
+            pf[nf * 4 + r] = p;
+            dsf[nf * 4 + r] = p * (accd[r] - dl[r]) * scale;
+          }
         }
-      }
-
-      // P^T -> a_lds; dV += P^T @ dO (B from dOt).
-#pragma unroll
-      for (int nf = 0; nf < NQ; ++nf) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int row = g * 4 + r;
-          int col = nf * 16 + cl;
-          *reinterpret_cast<unsigned short*>(
-              aw + row * TP + swz(row, col * 2)) =
-              float_to_bf16_bits(pt[nf][r]);
-        }
-      }
-#pragma unroll
-      for (int kk2 = 0; kk2 < FQTB / 32; ++kk2) {
-        bf16x8 pa = lds_frag(aw, cl, TP, (kk2 * 32 + g * 8) * 2);
+        // dV^T += dO^T P and dK^T += Q^T dS with P and dS as B operands
+        // straight from registers.
+        const bf16x8 pb = __builtin_convertvector(pf, bf16x8);
+        union {
+          bf16x8 h;
+          ushortx8 u;
+        } db;
+        db.h = __builtin_convertvector(dsf, bf16x8);
 #pragma unroll
         for (int hf = 0; hf < HF; ++hf) {
-          bf16x8 bd =
-              lds_frag(dot_lds, hf * 16 + cl, TP, (kk2 * 32 + g * 8) * 2);
-          acc_dv[si][hf] = mfma16x16x32_bf16(pa, bd, acc_dv[si][hf]);
+          acc_dv[si][hf] = mfma16x16x32_bf16(
+              frag_at(dot_lds + hf * 16 * TP + ft[hf & 1]), pb,
+              acc_dv[si][hf]);
+          acc_dk[si][hf] = mfma16x16x32_bf16(
+              frag_at(qt_lds + hf * 16 * TP + ft[hf & 1]), db.h,
+              acc_dk[si][hf]);
         }
-      }
-
-      // dP^T = V @ dO^T (B from do_lds rows).
+        // dS (scaled, bf16) into the shared [q][key] tile for dQ: constant
+        // offsets from one address per lane.
 #pragma unroll
-      for (int nf = 0; nf < NQ; ++nf) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int nf = 0; nf < NQ; ++nf) {
 #pragma unroll
-        for (int kk = 0; kk < KH; ++kk) {
-          bf16x8 bd =
-              lds_frag(do_lds, nf * 16 + cl, ROWB, (kk * 32 + g * 8) * 2);
-          acc = mfma16x16x32_bf16(vfrag[si][kk], bd, acc);
-        }
-        const float dl = delta_s[nf * 16 + cl];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dlg[nf][r] = pt[nf][r] * (acc[r] - dl);
-      }
-
-      // dS^T (scaled, bf16) -> a_lds (overwrite) and, transposed, into the
-      // shared dS tile: a lane's 4 keys are 8 contiguous bytes of row q.
-#pragma unroll
-      for (int nf = 0; nf < NQ; ++nf) {
-        ushortx4 pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int row = g * 4 + r;
-          int col = nf * 16 + cl;
-          pk[r] = float_to_bf16_bits(dlg[nf][r] * scale);
-          *reinterpret_cast<unsigned short*>(
-              aw + row * TP + swz(row, col * 2)) = pk[r];
-        }
-        const int qrow = nf * 16 + cl;
-        *reinterpret_cast<ushortx4*>(
-            ds_lds + qrow * DSP + swz(qrow, (k0 + g * 4) * 2)) = pk;
-      }
-      // dK += dS^T @ Q (B = Qt).
-#pragma unroll
-      for (int kk2 = 0; kk2 < FQTB / 32; ++kk2) {
-        bf16x8 da = lds_frag(aw, cl, TP, (kk2 * 32 + g * 8) * 2);
-#pragma unroll
-        for (int hf = 0; hf < HF; ++hf) {
-          bf16x8 bq =
-              lds_frag(qt_lds, hf * 16 + cl, TP, (kk2 * 32 + g * 8) * 2);
-          acc_dk[si][hf] = mfma16x16x32_bf16(da, bq, acc_dk[si][hf]);
+          for (int r = 0; r < 4; ++r) {
+            *reinterpret_cast<unsigned short*>(
+                dsw + (nf * 16 + r) * DSQ + si * NWF * 32) = db.u[nf * 4 + r];
+          }
         }
       }
     }
@@ -1400,8 +1431,8 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
 #pragma unroll
       for (int i = 0; i < TPW; ++i) acc_dq[i] = {0.f, 0.f, 0.f, 0.f};
       for (int kk2 = 0; kk2 < kact / 32; ++kk2) {
-        bf16x8 bs =
-            lds_frag(ds_lds, qs * 16 + cl, DSP, (kk2 * 32 + g * 8) * 2);
+        bf16x8 bs = frag_at(ds_lds + (qs * 16 + cl) * DSQ +
+                            (kk2 * 32 + g * 8) * 2);
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
           bf16x8 ak = lds_frag(kt_lds, (hf0 + i) * 16 + cl, DSP,
@@ -1435,29 +1466,32 @@ __global__ __launch_bounds__(NWF * WAVE_SIZE) void fa_bwd_fused_kernel(
         for (int qrow = q_lo; qrow <= q_hi; ++qrow) {
           const int key = qrow - doff;
           sum += bf16_bits_to_float(*reinterpret_cast<unsigned short*>(
-              ds_lds + qrow * DSP + swz(qrow, key * 2)));
+              ds_lds + qrow * DSQ + key * 2));
         }
         dacc[qb + doff + SP - 1] += sum;
       }
     }
   }
 
-  // dK/dV: every key row < S of this head is written once; strips past
-  // klen carry zero accumulators.
+  // dK/dV: every key row < S of this head is written once, 4 consecutive h
+  // of the lane's key per store; strips past klen carry zero accumulators.
 #pragma unroll
   for (int si = 0; si < SPW; ++si) {
+    const int key = (wid + si * NWF) * 16 + cl;
+    if (key >= S) continue;
+    const long tok = (long)b * S + key;
+    unsigned short* dkp = dk + tok * sdk + n * H + g * 4;
+    unsigned short* dvp = dv + tok * sdv + n * H + g * 4;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int key = (wid + si * NWF) * 16 + g * 4 + r;
-      if (key >= S) continue;
-      const long tok = (long)b * S + key;
-#pragma unroll
-      for (int hf = 0; hf < HF; ++hf) {
-        dk[tok * sdk + n * H + hf * 16 + cl] =
-            float_to_bf16_bits(acc_dk[si][hf][r]);
-        dv[tok * sdv + n * H + hf * 16 + cl] =
-            float_to_bf16_bits(acc_dv[si][hf][r]);
-      }
+    for (int hf = 0; hf < HF; ++hf) {
+      union {
+        ff_bf16x4 h;
+        ushortx4 u;
+      } ok, ov;
+      ok.h = __builtin_convertvector(acc_dk[si][hf], ff_bf16x4);
+      ov.h = __builtin_convertvector(acc_dv[si][hf], ff_bf16x4);
+      *reinterpret_cast<ushortx4*>(dkp + hf * 16) = ok.u;
+      *reinterpret_cast<ushortx4*>(dvp + hf * 16) = ov.u;
     }
   }
 
